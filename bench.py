@@ -29,7 +29,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-PEAK_BF16_TFLOPS = 2500.0   # dense bf16 MFMA peak, /opt/skills/guides/MI355X_MICROARCH.md:43
+PEAK_BF16_TFLOPS = 2500.0   # dense bf16 MFMA peak of the MI355X
 FWD_GFLOP_PER_IMG = 161.46  # DiT-L/2 forward, 2*MAC
 
 
@@ -79,7 +79,13 @@ def parse():
                     help="(internal) run only the secondary block and print its JSON: the main process starts this as a fresh child "
                          "so that a hang or a GPU fault in a secondary kernel cannot take the measured headline with it")
     ap.add_argument("--launch-timeout", type=int, default=3600, help="seconds before a self-launched multi-rank run is abandoned")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed sample() call returned on rank 0 as DIR/<name>.npy "
+                         "(float32, at most 64 MB; a fixed seeded subset of the images beyond that) so that two builds can be "
+                         "compared output for output: with the same arguments the inputs are identical from run to run")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if a.cu_reserve < 0 or a.cu_reserve % 8 or a.cu_reserve > 64:
         ap.error("--cu-reserve must be 0 or a multiple of 8 up to 64 (bsi_set_cu_reserve)")
     return a
@@ -527,6 +533,33 @@ def secondary_in_child(a):
         return {"error": f"{type(e).__name__}: {e}"}
 
 
+DUMP_LIMIT_BYTES = 64 * 2 ** 20
+
+
+def dump_outputs(dirname, arrays, limit=DUMP_LIMIT_BYTES):
+    """Write each tensor of `arrays` as dirname/<name>.npy (float64 stays float64, every other dtype becomes float32).  Beyond
+    `limit` bytes in all, every array keeps the same share of its leading-dimension rows, a fixed seeded choice kept in order, so
+    that two runs with the same arguments write the same rows.  Returns {name: {shape, dtype, rows, of_rows}} for the JSON line."""
+    import numpy as np
+
+    os.makedirs(dirname, exist_ok=True)
+    host = {k: v.detach().cpu() for k, v in arrays.items()}
+    host = {k: v if v.dtype == torch.float64 else v.float() for k, v in host.items()}
+    total = sum(v.numel() * v.element_size() for v in host.values())
+    share = min(1.0, limit / max(total, 1))
+    info = {}
+    for name, v in host.items():
+        rows = v.shape[0] if v.dim() else 1
+        if share < 1.0 and v.dim():
+            keep = max(1, int(rows * share))
+            idx = torch.randperm(rows, generator=torch.Generator().manual_seed(0))[:keep].sort().values
+            v = v[idx]
+        arr = v.contiguous().numpy()
+        np.save(os.path.join(dirname, name + ".npy"), arr)
+        info[name] = {"shape": list(arr.shape), "dtype": str(arr.dtype), "rows": int(arr.shape[0]) if arr.ndim else 1, "of_rows": rows}
+    return info
+
+
 def summary(line):
     """The numbers a reader of the line's TAIL must not miss (the driver keeps the last 2000 characters): sampling value, the train
     half of the metric, the per-rank rehearsal, the secondary values -- compact, last key of the line."""
@@ -731,6 +764,10 @@ def main():
                          "kernel": N.fc1_kernel_name(),
                          "launches": cnt, "avg_launch_ms": avg_ms, "flops_per_launch": flops_per_launch},
         }
+
+    if a.dump_outputs and rank == 0:
+        # what a caller of the timed path received from its last call (rank 0's chains; other ranks draw other noise)
+        line["dump_outputs"] = {"dir": a.dump_outputs, "arrays": dump_outputs(a.dump_outputs, {"samples": out})}
 
     if a.breakdown and rank == 0:
         names = list(N.PROF_CLASSES)
