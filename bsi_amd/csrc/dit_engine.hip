@@ -283,6 +283,18 @@ int check_forward_args(const bsi_dit_config* cfg, const bsi_dit_weights* w, int 
     return BSI_OK;
 }
 
+// Does a chain over Bh images give its rows the arithmetic of the chain over all B images?  The GEMMs choose their kernel and
+// split-K plan from M and from the CUs they may fill (cus for the one-stream call, cus_h inside the pair), and a few images per
+// call take split-K (fc2: 128 < M <= 2048), whose K slices sum in another order.
+bool same_gemm_plans(const bsi_dit_config* c, int B, int cus, int Bh, int cus_h) {
+    const DitDims d = dims_of(c);
+    const int dm = c->dim, M = B * d.tokens, Mh = Bh * d.tokens;
+    const int shapes[4][2] = {{3 * dm, dm}, {dm, dm}, {4 * dm, dm}, {dm, 4 * dm}};  // (N, K): qkv, out, fc1, fc2
+    for (const auto& nk : shapes)
+        if (bsi_gemm_ws_plan(M, nk[0], nk[1], cus) != bsi_gemm_ws_plan(Mh, nk[0], nk[1], cus_h)) return false;
+    return (M > 128) == (Mh > 128);  // the patch encoder (bsi_gemm_bf16): small-M tile or the large kernels
+}
+
 }  // namespace
 
 extern "C" int bsi_dit_forward(const bsi_dit_config* cfg, const bsi_dit_weights* w, int B, const float* mu,
@@ -379,6 +391,13 @@ extern "C" int bsi_dit_forward_pair(const bsi_dit_config* cfg, const bsi_dit_wei
     const DitDims d = dims_of(cfg);
     const size_t D = (size_t)cfg->C * cfg->H * cfg->W;
     const int Bh[2] = {(B + 1) / 2, B / 2};
+    {
+        // bit-identical to bsi_dit_forward for every B >= 2: where a half would run a GEMM with another kernel or split-K plan than
+        // the whole batch does (a few images per half), the evaluation is the one-stream chain on the caller's stream
+        const int cus = compute_cus(), cus_h = device_cus() - pair->h_cus < 8 ? 8 : device_cus() - pair->h_cus;
+        if (!same_gemm_plans(cfg, B, cus, Bh[0], cus_h) || !same_gemm_plans(cfg, B, cus, Bh[1], cus_h))
+            return bsi_dit_forward(cfg, w, B, mu, mod, mod_rows, c_in, c_skip, c_out, coef_stride, out, workspace, nullptr, stream);
+    }
     // the two halves' chains: images [0, Bh0) and [Bh0, B), each with a workspace of its own inside the caller's
     std::vector<Op> ch[2];
     const size_t ws0 = carve(cfg, Bh[0], nullptr).total;

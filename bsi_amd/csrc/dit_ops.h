@@ -36,6 +36,9 @@ int bsi_attention_bwd_drop(const void* qkv, int ld_qkv, const void* out, const v
                            const void* maskw = nullptr, float* bias_rows = nullptr);
 // gemm_bf16.hip: can the MUL_GELUGRAD GEMM of this shape write bsi_gemm_args::colsum_rows?
 bool bsi_gemm_emits_colsum(int M, int K);
+// gemm_bf16.hip: the kernel / split-K plan of a plain bf16 epilogue through bsi_gemm_bf16_ws on `cus` compute units
+// (split count > 1, else 1 for M > 128 and 0 for the small-M tile)
+int bsi_gemm_ws_plan(int M, int N, int K, int cus);
 // attention_bwd_x.hip: the single-sweep backward (256 tokens, head dim 64; dropout off, or on with the mask words)
 // bias_rows (or null): [B][3 * heads * 64] fp32 per-image column sums of dqkv (the qkv bias gradient's slabs)
 int bsi_attention_bwd_exchange(const void* qkv, int ld_qkv, const void* out, const void* dout, int ld_o, const float* lse, int B,

@@ -1413,6 +1413,14 @@ extern "C" int bsi_gemm_set_variant(int v) {
 // does the MUL_GELUGRAD GEMM of this shape run the kernel whose epilogue can emit column sums (bsi_gemm_args::colsum_rows)?
 bool bsi_gemm_emits_colsum(int M, int K) { return g_variant == 12 && M > 128 && K >= 128 && K % 64 == 0; }
 
+// which arithmetic bsi_gemm_bf16_ws gives an output row of a plain bf16 epilogue of this shape when the persistent kernels may fill
+// `cus` CUs: the split count (> 1) of the split-K path, else 1 for the large-M kernels (M > 128) and 0 for the small-M tile.  Two
+// problems with the same N, K and plan compute every row with the same sums in the same order.
+int bsi_gemm_ws_plan(int M, int N, int K, int cus) {
+    const int sp = splitk_plan(M, N, K, cus);
+    return sp > 1 ? sp : (M > 128 ? 1 : 0);
+}
+
 extern "C" int bsi_gemm_bf16(const bsi_gemm_args* a, bsi_stream_t stream) {
     BSI_CHECK_ARG(a != nullptr, "bsi_gemm_bf16: null args");
     BSI_CHECK_ARG(a->M > 0 && a->N > 0 && a->K > 0, "bsi_gemm_bf16: empty problem M=%d N=%d K=%d", a->M, a->N, a->K);

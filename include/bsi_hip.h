@@ -384,13 +384,15 @@ int bsi_dit_forward(const bsi_dit_config* cfg, const bsi_dit_weights* w /*host*/
                     const float* mod, int mod_rows, const float* c_in, const float* c_skip, const float* c_out,
                     int coef_stride, float* out, void* workspace, float* tokens_out, bsi_stream_t stream);
 
-/* Two-resource evaluation: the same result as bsi_dit_forward (bit for bit: every row's arithmetic is independent of the batch it
- * is launched in), with the batch split into two halves whose launches are interleaved over a PAIR of CU-masked streams
- * (hipExtStreamCreateWithCUMask): the matrix-pipe-bound launches (GEMMs, attention) on the large partition G, the HBM-bound ones
+/* Two-resource evaluation: the same result as bsi_dit_forward on the caller's stream, bit for bit, for every B >= 2, with the batch
+ * split into two halves whose launches are interleaved over a PAIR of CU-masked streams (hipExtStreamCreateWithCUMask): the matrix-pipe-bound launches (GEMMs, attention) on the large partition G, the HBM-bound ones
  * (prologue, LayerNorm+modulate passes, final kernel) of the OTHER half on the small partition H (h_cus compute units, a multiple
  * of 8 = the same number on every XCD), handed over by events.  While G multiplies for one half, H streams for the other: the loop
  * of bsi.py:312-336 / dit.py:96-103 no longer alternates between an idle memory system and idle matrix pipes.  The caller's stream
  * forks into the pair at entry and joins at exit; workspace: bsi_dit_workspace_bytes(cfg, B) bytes as for bsi_dit_forward.
+ * A row's arithmetic depends on the batch only through the GEMM plans (kernel: M <= 128 or not; split-K slices: 128 < M <= 2048,
+ * K >= 2048, counted from the CUs the partition leaves): where either half would get another plan than the whole batch (a few images
+ * per half, e.g. DiT-L/2 at B = 16 or 17 on 256 CUs), the call runs bsi_dit_forward's single chain on the caller's stream instead.
  * flags: BSI_PAIR_ATTN_ON_H = attention launches on H instead of G. */
 typedef struct bsi_cu_pair bsi_cu_pair;
 #define BSI_PAIR_ATTN_ON_H 1
