@@ -65,11 +65,13 @@ class ConvPackDesc(C.Structure):
 
 
 class UNetConfig(C.Structure):
-    _fields_ = [(k, C.c_int) for k in ("C", "H", "W", "dim", "levels", "heads", "ff_nmin", "ff_nmax", "emb_size", "c_dim")]
+    _fields_ = [(k, C.c_int) for k in ("C", "H", "W", "dim", "levels", "heads", "ff_nmin", "ff_nmax", "emb_size", "c_dim",
+                                          "block_heads")]
 
 
 class UNetResBlockWeights(C.Structure):
-    _fields_ = [(k, C.c_void_p) for k in ("gn_w", "gn_b", "conv1_w", "conv1_b", "conv2_w", "conv2_b")]
+    _fields_ = [(k, C.c_void_p) for k in ("gn_w", "gn_b", "conv1_w", "conv1_b", "conv2_w", "conv2_b", "agn_w", "agn_b",
+                                          "aqkv_w", "aqkv_b", "aout_w", "aout_b")]
 
 
 class UNetWeights(C.Structure):
@@ -80,7 +82,7 @@ class UNetWeights(C.Structure):
 
 
 class UNetResBlockWeightsT(C.Structure):
-    _fields_ = [(k, C.c_void_p) for k in ("conv1_wT", "conv2_wT", "skip_wT")]
+    _fields_ = [(k, C.c_void_p) for k in ("conv1_wT", "conv2_wT", "skip_wT", "aqkv_wT", "aout_wT")]
 
 
 class UNetWeightsT(C.Structure):
@@ -88,7 +90,8 @@ class UNetWeightsT(C.Structure):
 
 
 class UNetResBlockGrads(C.Structure):
-    _fields_ = [(k, C.c_void_p) for k in ("gn_w", "gn_b", "conv1_w", "conv1_b", "conv2_w", "conv2_b", "skip_w")]
+    _fields_ = [(k, C.c_void_p) for k in ("gn_w", "gn_b", "conv1_w", "conv1_b", "conv2_w", "conv2_b", "skip_w",
+                                          "agn_w", "agn_b", "aqkv_w", "aqkv_b", "aout_w", "aout_b")]
 
 
 class UNetGrads(C.Structure):

@@ -17,12 +17,18 @@ namespace {
 
 template <int DH>
 __device__ __forceinline__ int k_chunk_swz(int row, int chunk) {  // 16-B chunk index within a K row
-    if constexpr (DH == 64) return chunk ^ ((row >> 1) & 7);
+    // 64-B rows (DH 32): four rows share a 256-B bank window; rows r, r+4, r+8, r+12 land in one 64-B quarter, so their chunk keys
+    // 0, 3, 2, 1 (= -(r >> 2) & 3) keep each 16-lane group of the row reads (ds_read_b128: 8 rows x chunk g, 8 rows x chunk g ^ 1)
+    // on 16 distinct 16-B slots
+    if constexpr (DH == 32) return chunk ^ (-(row >> 2) & 3);
+    else if constexpr (DH == 64) return chunk ^ ((row >> 1) & 7);
     else return chunk ^ (row & 15);
 }
 template <int DH>
 __device__ __forceinline__ int v_block_swz(int row, int blk) {  // 32-B block index within a V row
-    if constexpr (DH == 64) return blk ^ ((row >> 1) & 3);
+    // DH 32: a half-wave of the transposed reads touches rows 4g + q' (8 rows) x one 32-B block; rows r and r + 4 share a 64-B quarter
+    if constexpr (DH == 32) return blk ^ ((row >> 2) & 1);
+    else if constexpr (DH == 64) return blk ^ ((row >> 1) & 3);
     else return blk ^ (row & 7);
 }
 
@@ -314,7 +320,7 @@ bool bsi_attention_uses_mask_words(int tokens, int dh) {
 static int attention_fwd_impl(const void* qkv, int ld_qkv, int B, int tokens, int heads, int dh, void* out, int ld_out,
                               float* lse, DropCfg dc, bsi_stream_t stream, void* maskw = nullptr, bool mask_ready = false) {
     BSI_CHECK_ARG(qkv && out && B > 0 && heads > 0, "bsi_attention_fwd: bad args");
-    BSI_CHECK_ARG(dh == 64 || dh == 128, "bsi_attention_fwd: head dim %d unsupported (64 or 128)", dh);
+    BSI_CHECK_ARG(dh == 32 || dh == 64 || dh == 128, "bsi_attention_fwd: head dim %d unsupported (32, 64 or 128)", dh);
     BSI_CHECK_ARG(tokens > 0 && tokens % 64 == 0, "bsi_attention_fwd: tokens=%d must be a multiple of 64", tokens);
     BSI_CHECK_ARG(ld_qkv % 8 == 0 && ld_qkv >= 3 * heads * dh && ld_out % 8 == 0 && ld_out >= heads * dh,
                   "bsi_attention_fwd: bad leading dimensions");
@@ -332,6 +338,14 @@ static int attention_fwd_impl(const void* qkv, int ld_qkv, int B, int tokens, in
             return bsi_attention_fwd_persistent(qkv, ld_qkv, B, heads, out, ld_out, lse, dc, maskw, mask_ready, s);
         if (tokens <= 256 && !chunked) return launch_attn<64, 64, true>(q, ld_qkv, B, tokens, heads, o, ld_out, lse, dc, s);
         return launch_attn<64, 64>(q, ld_qkv, B, tokens, heads, o, ld_out, lse, dc, s);
+    }
+    if (dh == 32) {
+        // the VDM-UNet's per-block attention (4 heads of 32 channels, 64 .. 1024 positions): one 16x16x32 MFMA per score tile, so
+        // the kernel is bound by the softmax's VALU / transcendental work.  Up to 256 tokens K and V are staged once (32 KB),
+        // longer sequences in 128-key chunks (64 when the count is not a multiple of 128).
+        if (tokens <= 256) return launch_attn<32, 64, true>(q, ld_qkv, B, tokens, heads, o, ld_out, lse, dc, s);
+        if (tokens % 128 == 0) return launch_attn<32, 128>(q, ld_qkv, B, tokens, heads, o, ld_out, lse, dc, s);
+        return launch_attn<32, 64>(q, ld_qkv, B, tokens, heads, o, ld_out, lse, dc, s);
     }
     if (tokens % 128 == 0) return launch_attn<128, 128>(q, ld_qkv, B, tokens, heads, o, ld_out, lse, dc, s);
     return launch_attn<128, 64>(q, ld_qkv, B, tokens, heads, o, ld_out, lse, dc, s);

@@ -16,7 +16,11 @@ namespace {
 
 template <int DH>
 __device__ __forceinline__ int swz(int r) {
-    if constexpr (DH == 64) return ((r >> 1) & 3) << 1;
+    // 64-B rows (DH 32): rows r, r+4, r+8, r+12 share a 64-B quarter of the 256-B bank window; keys 0, 3, 2, 1 make the row reads
+    // (16-lane groups: 8 rows x chunk g, 8 rows x chunk g ^ 1) and the transposed reads (half-wave: rows 4g + q', chunk pair 2dt,
+    // 2dt + 1 -- the keys of r and r + 4 differ in bit 1) conflict-free
+    if constexpr (DH == 32) return -(r >> 2) & 3;
+    else if constexpr (DH == 64) return ((r >> 1) & 3) << 1;
     else return (r & 7) << 1;
 }
 template <int DH>
@@ -32,7 +36,7 @@ __global__ __launch_bounds__(512) void attention_bwd_stream_kernel(const __bf16*
                                                                    int ld_o, const float* __restrict__ lse, int T, int heads,
                                                                    __bf16* __restrict__ dqkv, int ld_dqkv, float scale) {
     constexpr int RB = DH * 2, CPR = DH / 8, KS = DH / 32, DT = DH / 16;
-    constexpr int JR = DH == 64 ? 2 : 1;      // 16-row tiles owned by a wave
+    constexpr int JR = DH <= 64 ? 2 : 1;      // 16-row tiles owned by a wave
     constexpr int LPT = 2 * 64 * CPR / 512;   // 16-B loads per thread per streamed chunk (two tiles)
     extern __shared__ __attribute__((aligned(16))) char lds[];
     char* TA = lds;
@@ -294,7 +298,7 @@ __global__ __launch_bounds__(512) void attention_bwd_stream_kernel(const __bf16*
 template <int DH>
 int launch_stream(const __bf16* qkv, int ld_qkv, const __bf16* o, const __bf16* dout, int ld_o, const float* lse, int B, int T,
                   int heads, __bf16* dqkv, int ld_dqkv, hipStream_t s) {
-    constexpr int JR = DH == 64 ? 2 : 1;
+    constexpr int JR = DH <= 64 ? 2 : 1;
     const size_t lds = (size_t)2 * 64 * DH * 2 + (size_t)2 * T * sizeof(float);
     auto kern = attention_bwd_stream_kernel<DH>;
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -310,7 +314,7 @@ int launch_stream(const __bf16* qkv, int ld_qkv, const __bf16* o, const __bf16* 
 extern "C" int bsi_attention_bwd_long(const void* qkv, int ld_qkv, const void* out, const void* dout, int ld_o, const float* lse,
                                       int B, int tokens, int heads, int dh, void* dqkv, int ld_dqkv, bsi_stream_t stream) {
     BSI_CHECK_ARG(qkv && out && dout && lse && dqkv && B > 0 && heads > 0, "bsi_attention_bwd_long: bad args");
-    BSI_CHECK_ARG(dh == 64 || dh == 128, "bsi_attention_bwd_long: head dim %d unsupported (64 or 128)", dh);
+    BSI_CHECK_ARG(dh == 32 || dh == 64 || dh == 128, "bsi_attention_bwd_long: head dim %d unsupported (32, 64 or 128)", dh);
     BSI_CHECK_ARG(tokens > 0 && tokens % 64 == 0 && tokens <= 8192, "bsi_attention_bwd_long: tokens=%d must be a multiple of 64, <= 8192",
                   tokens);
     BSI_CHECK_ARG(ld_qkv % 8 == 0 && ld_o % 8 == 0 && ld_dqkv % 4 == 0, "bsi_attention_bwd_long: bad leading dimensions");
@@ -319,6 +323,7 @@ extern "C" int bsi_attention_bwd_long(const void* qkv, int ld_qkv, const void* o
     const __bf16* o = reinterpret_cast<const __bf16*>(out);
     const __bf16* d = reinterpret_cast<const __bf16*>(dout);
     __bf16* dq = reinterpret_cast<__bf16*>(dqkv);
+    if (dh == 32) return launch_stream<32>(q, ld_qkv, o, d, ld_o, lse, B, tokens, heads, dq, ld_dqkv, s);
     if (dh == 64) return launch_stream<64>(q, ld_qkv, o, d, ld_o, lse, B, tokens, heads, dq, ld_dqkv, s);
     return launch_stream<128>(q, ld_qkv, o, d, ld_o, lse, B, tokens, heads, dq, ld_dqkv, s);
 }

@@ -38,6 +38,7 @@ struct UWs {
     char* qkv;    // bf16 [M, 3 dim]
     float* h[3];  // fp32 [M, dim] rotating feature maps, each followed by its GroupNorm partials (map_bytes: conv epilogue -> bsi_groupnorm_apply_nhwc)
     float* skips; // fp32 [levels][M, dim], same
+    float* bmap;  // block_heads > 0: fp32 [M, dim] + partials, a residual block's output in front of its Residual(GroupNorm -> Attention2D)
     size_t map_bytes, fmap_bytes;  // one feature map without / with its partials
     // split GroupNorm of the up blocks (gn_split): per level the normalised and the raw bf16 cat(x, skip), [M, 2 dim] each -- the skip
     // half (columns dim ..) is written on the way DOWN by the pass that reads the skip tensor anyway, the x half on the way up
@@ -59,9 +60,10 @@ inline bool gn_fuse_on(const bsi_unet_config* c) {
 // 18 % fewer bytes, but the halves are 256-B pieces at a 512-B pitch of the [M, 2 dim] operand of conv1 and stream at 4.8 TB/s where
 // whole rows run at 6.2.  Contiguous halves need a two-source operand in the slab convolution; and the level buffers cost 17 GB of
 // workspace at 512 images.
+// Not with per-block attention: the plain per-block GroupNorm is kept there.
 inline bool gn_split_on(const bsi_unet_config* c) {
     static const bool on = getenv("BSI_UNET_GN_SPLIT") != nullptr;
-    return on && gn_fuse_on(c) && c->levels > 0;
+    return on && gn_fuse_on(c) && c->levels > 0 && c->block_heads == 0;
 }
 
 inline UWs carve(const bsi_unet_config* c, int B, void* base) {
@@ -81,6 +83,7 @@ inline UWs carve(const bsi_unet_config* c, int B, void* base) {
     w.fmap_bytes = w.map_bytes + au((M + 127) / 128 * (dim / 4) * 2 * 4);  // + (mean, M2) per 128 pixels x 4 channels
     for (int i = 0; i < 3; ++i) { w.h[i] = reinterpret_cast<float*>(p + off); off += w.fmap_bytes; }
     w.skips = reinterpret_cast<float*>(p + off); off += w.fmap_bytes * c->levels;
+    w.bmap = reinterpret_cast<float*>(p + off); off += c->block_heads > 0 ? w.fmap_bytes : 0;
     w.up_bytes = gn_split_on(c) ? au(M * 2 * dim * 2) : 0;
     w.upa = p + off; off += w.up_bytes * c->levels;
     w.upraw = p + off; off += w.up_bytes * c->levels;
@@ -160,6 +163,12 @@ extern "C" int bsi_unet_forward(const bsi_unet_config* cfg, const bsi_unet_weigh
     const int dim = cfg->dim, H = cfg->H, W = cfg->W, L = cfg->levels;
     BSI_CHECK_ARG(dim % 32 == 0 && (dim == 64 || dim == 128) && dim % cfg->heads == 0 && (d.dh == 64 || d.dh == 128) && d.HW % 64 == 0,
                   "bsi_unet_forward: unsupported geometry dim=%d heads=%d HW=%d", dim, cfg->heads, d.HW);
+    BSI_CHECK_ARG(cfg->block_heads == 0 || (cfg->block_heads > 0 && dim == 32 * cfg->block_heads),
+                  "bsi_unet_forward: per-block attention needs head dim 32 (dim=%d, block_heads=%d)", dim, cfg->block_heads);
+    for (int i = 0; cfg->block_heads > 0 && i < d.nblocks; ++i)
+        BSI_CHECK_ARG(w->blocks[i].agn_w && w->blocks[i].agn_b && w->blocks[i].aqkv_w && w->blocks[i].aqkv_b && w->blocks[i].aout_w &&
+                          w->blocks[i].aout_b,
+                      "bsi_unet_forward: block %d: per-block attention weights missing", i);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     UWs ws = carve(cfg, B, workspace);
     const int fstride = d.nblocks * 2 * dim;
@@ -185,7 +194,9 @@ extern "C" int bsi_unet_forward(const bsi_unet_config* cfg, const bsi_unet_weigh
     // residual block (residual_block.py:61-64): out = skip(x) + conv2(silu(film(conv1(silu(gn(x))))))
     // skip_level >= 0 (gn_split): x1 IS skip tensor `skip_level`; its pass also writes the skip half of that level's up block.
     // up_level >= 0: an up block, x2 = skip tensor `up_level`.
-    auto resblock = [&](int blk, const float* x1, const float* x2, float* dst, int skip_level, int up_level) -> int {
+    // block_heads > 0: the block's output goes to ws.bmap and its Residual(GroupNorm -> Attention2D) (residual_block.py:50-64) writes
+    // `dst`, so skip tensors and the next block's GroupNorm see the post-attention map; every map keeps its own partials.
+    auto resblock_conv = [&](int blk, const float* x1, const float* x2, float* dst, int skip_level, int up_level) -> int {
         const bsi_unet_resblock_weights& rb = w->blocks[blk];
         const int cin2 = x2 ? dim : 0;
         const void* a_in = ws.a;      // conv1 operand
@@ -224,6 +235,22 @@ extern "C" int bsi_unet_forward(const bsi_unet_config* cfg, const bsi_unet_weigh
         return conv(ws.y, x2 ? raw_in : nullptr, rb.conv2_w, rb.conv2_b, ws.zeros, dst, nullptr, 0, 0, x2 ? nullptr : x1, B, H, W, dim,
                     x2 ? 2 * dim : 0, dim, 9, BSI_CONV_BIAS_RESID_F32, stream, part_of(dst));
     };
+    // x + to_out(SDPA(to_qkv(GroupNorm(x))))  (attention.py:32-41): GroupNorm without SiLU, no dropout on the attention weights
+    auto attention = [&](const float* x, const float* gw, const float* gb, const void* qkv_w, const float* qkv_b, const void* out_w,
+                         const float* out_b, int heads, float* dst) -> int {
+        TRY(groupnorm(x, nullptr, 0, gw, gb, 0, nullptr));
+        TRY(conv(ws.a, nullptr, qkv_w, qkv_b, ws.zeros, ws.qkv, nullptr, 0, 0, nullptr, B, H, W, dim, 0, 3 * dim, 9, BSI_CONV_BIAS_BF16,
+                 stream));
+        TRY(bsi_attention_fwd(ws.qkv, 3 * dim, B, d.HW, heads, dim / heads, ws.y, dim, stream));
+        return conv(ws.y, nullptr, out_w, out_b, ws.zeros, dst, nullptr, 0, 0, x, B, H, W, dim, 0, dim, 9, BSI_CONV_BIAS_RESID_F32, stream,
+                    part_of(dst));
+    };
+    auto resblock = [&](int blk, const float* x1, const float* x2, float* dst, int skip_level, int up_level) -> int {
+        if (cfg->block_heads == 0) return resblock_conv(blk, x1, x2, dst, skip_level, up_level);
+        const bsi_unet_resblock_weights& rb = w->blocks[blk];
+        TRY(resblock_conv(blk, x1, x2, ws.bmap, skip_level, up_level));
+        return attention(ws.bmap, rb.agn_w, rb.agn_b, rb.aqkv_w, rb.aqkv_b, rb.aout_w, rb.aout_b, cfg->block_heads, dst);
+    };
     TRY(conv(ws.xin, nullptr, w->enc_w, w->enc_b, ws.zeros, h, nullptr, 0, 0, nullptr, B, H, W, d.cin_pad, 0, dim, 9,
              BSI_CONV_BIAS_RESID_F32, stream, part_of(h)));
     for (int i = 0; i < L; ++i) {  // down path: every block's output is also a skip tensor (simplified_unet.py:36-39)
@@ -234,14 +261,9 @@ extern "C" int bsi_unet_forward(const bsi_unet_config* cfg, const bsi_unet_weigh
     // centre: ResBlock, Residual(GroupNorm -> Attention2D), ResBlock (vdm_unet.py:80-89)
     TRY(resblock(L, h, nullptr, ws.h[cur], L - 1, -1));  // reads the last skip tensor
     h = ws.h[cur];
-    TRY(groupnorm(h, nullptr, 0, w->agn_w, w->agn_b, 0, nullptr));
-    TRY(conv(ws.a, nullptr, w->aqkv_w, w->aqkv_b, ws.zeros, ws.qkv, nullptr, 0, 0, nullptr, B, H, W, dim, 0, 3 * dim, 9,
-             BSI_CONV_BIAS_BF16, stream));
-    TRY(bsi_attention_fwd(ws.qkv, 3 * dim, B, d.HW, cfg->heads, d.dh, ws.y, dim, stream));
     {
         float* dst = ws.h[cur ^ 1];
-        TRY(conv(ws.y, nullptr, w->aout_w, w->aout_b, ws.zeros, dst, nullptr, 0, 0, h, B, H, W, dim, 0, dim, 9, BSI_CONV_BIAS_RESID_F32,
-                 stream, part_of(dst)));
+        TRY(attention(h, w->agn_w, w->agn_b, w->aqkv_w, w->aqkv_b, w->aout_w, w->aout_b, cfg->heads, dst));
         h = dst;
         cur ^= 1;
     }

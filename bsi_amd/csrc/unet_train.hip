@@ -6,6 +6,8 @@
 // Tape per residual block and pixel: a = bf16 silu(GN(x)) [Cx], (up blocks: raw = bf16 x [2 dim]), h1 = bf16 conv1 output
 // [dim], y = bf16 dropout(silu(film(h1))) [dim], out fp32 [dim]  = 1.25 MB (2 MB for an up block) per 32x32 image at
 // dim 128: 109 MB per image for the 67-block UNet of config/experiment/cifar10-vdm.yaml, 14 GB at 128 images per GPU.
+// With per-block attention (block_heads > 0) every block adds its Residual(GroupNorm -> Attention2D) tape: the stage's fp32 input,
+// bf16 GroupNorm output, qkv and attention output, the LSE and a GroupNorm statistics slot (+1.75 MB per block and 32x32 image).
 #include "common.h"
 #include "dit_ops.h"
 #include "unet_ops.h"
@@ -41,6 +43,14 @@ struct BlockTape {
     float* out;
 };
 
+struct AttnTape {  // per-block Residual(GroupNorm -> Attention2D); out = in + to_out(attention)
+    float* in;     // fp32 [M, dim]  the residual block's output
+    char* agn;     // bf16 [M, dim]
+    char* qkv;     // bf16 [M, 3 dim]
+    char* ay;      // bf16 [M, dim]
+    float* lse;    // fp32 [B, block_heads, HW]
+};
+
 struct UTape {
     char* zeros;
     char* xin;      // bf16 [M, cin_pad]
@@ -62,6 +72,8 @@ struct UTape {
     size_t gnpart_stride;  // floats per map
     char* blocks;
     size_t plain_bytes, up_bytes, total;
+    char* battn;        // block_heads > 0: [nblocks] AttnTape regions of battn_bytes
+    size_t battn_bytes;
 };
 
 inline UTape carve_tape(const bsi_unet_config* c, int B, void* base) {
@@ -84,13 +96,20 @@ inline UTape carve_tape(const bsi_unet_config* c, int B, void* base) {
     t.ay = p + off; off += au(M * dim * 2);
     t.lse = reinterpret_cast<float*>(p + off); off += au((size_t)B * c->heads * d.HW * 4);
     t.hatt = reinterpret_cast<float*>(p + off); off += au(M * dim * 4);
-    t.gnstats = reinterpret_cast<float*>(p + off); off += au((size_t)(d.nblocks + 1) * B * 64 * 4);
+    // block_heads > 0 appends nblocks slots to both: statistics of block i's attention GroupNorm at nblocks + 1 + i, partials of
+    // block i's stage input at nblocks + 2 + i
+    const int nattn = c->block_heads > 0 ? d.nblocks : 0;
+    t.gnstats = reinterpret_cast<float*>(p + off); off += au((size_t)(d.nblocks + 1 + nattn) * B * 64 * 4);
     t.gnpart_stride = au((M + 127) / 128 * (dim / 4) * 2 * 4) / 4;
-    t.gnpart = reinterpret_cast<float*>(p + off); off += t.gnpart_stride * 4 * (d.nblocks + 2);
+    t.gnpart = reinterpret_cast<float*>(p + off); off += t.gnpart_stride * 4 * (d.nblocks + 2 + nattn);
     t.blocks = p + off;
     t.plain_bytes = au(M * dim * 2) * 3 + au(M * dim * 4);
     t.up_bytes = au(M * 2 * dim * 2) * 2 + au(M * dim * 2) * 2 + au(M * dim * 4);
     off += t.plain_bytes * (d.L + 2) + t.up_bytes * d.L;
+    t.battn = p + off;
+    t.battn_bytes = c->block_heads > 0 ? au(M * dim * 4) + au(M * dim * 2) * 2 + au(M * 3 * dim * 2) + au((size_t)B * c->block_heads * d.HW * 4)
+                                       : 0;
+    off += t.battn_bytes * nattn;
     t.total = off;
     return t;
 }
@@ -114,8 +133,22 @@ inline BlockTape block_tape(const UTape& t, const UD& d, int blk) {
     return b;
 }
 
+inline AttnTape attn_tape(const UTape& t, const UD& d, int blk) {
+    AttnTape a;
+    const size_t M = d.M, dim = d.dim;
+    char* p = t.battn + t.battn_bytes * blk;
+    size_t off = 0;
+    a.in = reinterpret_cast<float*>(p + off); off += au(M * dim * 4);
+    a.agn = p + off; off += au(M * dim * 2);
+    a.qkv = p + off; off += au(M * 3 * dim * 2);
+    a.ay = p + off; off += au(M * dim * 2);
+    a.lse = reinterpret_cast<float*>(p + off);
+    return a;
+}
+
 struct UBwd {
     float* dcur[2];  // fp32 [M, dim]
+    float* datt;     // block_heads > 0: fp32 [M, dim], gradient of a block's attention-stage input
     float* dskips;   // fp32 [L][M, dim]
     float* dcat;     // fp32 [M, 2 dim]
     char* g;         // bf16 [M, dim]
@@ -142,6 +175,7 @@ inline UBwd carve_bwd(const bsi_unet_config* c, int B, void* base) {
     size_t off = 0;
     const size_t M = d.M, dim = d.dim, cd = c->c_dim;
     for (int i = 0; i < 2; ++i) { w.dcur[i] = reinterpret_cast<float*>(p + off); off += au(M * dim * 4); }
+    w.datt = reinterpret_cast<float*>(p + off); off += c->block_heads > 0 ? au(M * dim * 4) : 0;
     w.skip_stride = au(M * dim * 4);
     w.dskips = reinterpret_cast<float*>(p + off); off += w.skip_stride * d.L;
     w.dcat = reinterpret_cast<float*>(p + off); off += au(M * 2 * dim * 4);
@@ -201,6 +235,8 @@ int check_geometry(const bsi_unet_config* cfg, const UD& d, const char* who) {
                       cfg->emb_size <= 64 && cfg->emb_size % 2 == 0 && cfg->c_dim % 64 == 0,
                   "%s: unsupported geometry dim=%d heads=%d HW=%d emb=%d c_dim=%d", who, cfg->dim, cfg->heads, d.HW, cfg->emb_size,
                   cfg->c_dim);
+    BSI_CHECK_ARG(cfg->block_heads == 0 || (cfg->block_heads > 0 && cfg->dim == 32 * cfg->block_heads),
+                  "%s: per-block attention needs head dim 32 (dim=%d, block_heads=%d)", who, cfg->dim, cfg->block_heads);
     return BSI_OK;
 }
 
@@ -262,7 +298,7 @@ extern "C" int bsi_unet_train_forward(const bsi_unet_config* cfg, const bsi_unet
     };
     TRY(conv(tp.xin, nullptr, w->enc_w, w->enc_b, tp.zeros, tp.henc, nullptr, B, H, W, d.cin_pad, 0, dim, 9, BSI_CONV_BIAS_RESID_F32,
              stream, part(0)));
-    auto resblock = [&](int blk, const float* x1, int x1p, const float* x2, int x2p) -> int {
+    auto resblock_conv = [&](int blk, const float* x1, int x1p, const float* x2, int x2p, float* dst, int dstp) -> int {
         const bsi_unet_resblock_weights& rb = w->blocks[blk];
         BlockTape bt = block_tape(tp, d, blk);
         const int cin2 = x2 ? dim : 0;
@@ -271,8 +307,29 @@ extern "C" int bsi_unet_train_forward(const bsi_unet_config* cfg, const bsi_unet
                  stream));
         TRY(bsi_film_silu_drop(bt.h1, M, dim, d.HW, tp.film + (size_t)blk * 2 * dim, B, d.F, make_drop(dropout_p, seed, blk), bt.y,
                                stream));
-        return conv(bt.y, x2 ? bt.raw : nullptr, rb.conv2_w, rb.conv2_b, tp.zeros, bt.out, x2 ? nullptr : x1, B, H, W, dim,
-                    x2 ? 2 * dim : 0, dim, 9, BSI_CONV_BIAS_RESID_F32, stream, part(2 + blk));
+        return conv(bt.y, x2 ? bt.raw : nullptr, rb.conv2_w, rb.conv2_b, tp.zeros, dst, x2 ? nullptr : x1, B, H, W, dim,
+                    x2 ? 2 * dim : 0, dim, 9, BSI_CONV_BIAS_RESID_F32, stream, part(dstp));
+    };
+    // x + to_out(SDPA(to_qkv(GroupNorm(x))))  (attention.py:32-41); x has GroupNorm partial slot xp, out gets slot outp
+    auto attention = [&](const float* x, int xp, const float* gw, const float* gb, const void* qkv_w, const float* qkv_b, const void* out_w,
+                         const float* out_b, int heads, char* agn, char* qkv, char* ay, float* lse, float* stats, float* out, int outp) -> int {
+        TRY(groupnorm(x, xp, nullptr, 0, gw, gb, 0, agn, nullptr, stats));
+        TRY(conv(agn, nullptr, qkv_w, qkv_b, tp.zeros, qkv, nullptr, B, H, W, dim, 0, 3 * dim, 9, BSI_CONV_BIAS_BF16, stream));
+        TRY(bsi_attention_fwd_lse(qkv, 3 * dim, B, d.HW, heads, dim / heads, ay, dim, lse, stream));
+        return conv(ay, nullptr, out_w, out_b, tp.zeros, out, x, B, H, W, dim, 0, dim, 9, BSI_CONV_BIAS_RESID_F32, stream, part(outp));
+    };
+    // block_heads > 0: conv2 writes the stage input (attn_tape.in) and the stage writes the block output (block_tape.out)
+    auto resblock = [&](int blk, const float* x1, int x1p, const float* x2, int x2p) -> int {
+        const bsi_unet_resblock_weights& rb = w->blocks[blk];
+        BlockTape bt = block_tape(tp, d, blk);
+        if (cfg->block_heads > 0) {
+            const AttnTape at = attn_tape(tp, d, blk);
+            const int inp = d.nblocks + 2 + blk;
+            TRY(resblock_conv(blk, x1, x1p, x2, x2p, at.in, inp));
+            return attention(at.in, inp, rb.agn_w, rb.agn_b, rb.aqkv_w, rb.aqkv_b, rb.aout_w, rb.aout_b, cfg->block_heads, at.agn, at.qkv, at.ay,
+                             at.lse, tp.gnstats + (size_t)(d.nblocks + 1 + blk) * B * 64, bt.out, 2 + blk);
+        }
+        return resblock_conv(blk, x1, x1p, x2, x2p, bt.out, 2 + blk);
     };
     const float* h = tp.henc;
     int hp = 0;
@@ -284,10 +341,8 @@ extern "C" int bsi_unet_train_forward(const bsi_unet_config* cfg, const bsi_unet
     TRY(resblock(L, h, hp, nullptr, 0));
     h = block_tape(tp, d, L).out;
     hp = 2 + L;
-    TRY(groupnorm(h, hp, nullptr, 0, w->agn_w, w->agn_b, 0, tp.agn, nullptr, tp.gnstats + (size_t)d.nblocks * B * 64));
-    TRY(conv(tp.agn, nullptr, w->aqkv_w, w->aqkv_b, tp.zeros, tp.qkv, nullptr, B, H, W, dim, 0, 3 * dim, 9, BSI_CONV_BIAS_BF16, stream));
-    TRY(bsi_attention_fwd_lse(tp.qkv, 3 * dim, B, d.HW, cfg->heads, d.dh, tp.ay, dim, tp.lse, stream));
-    TRY(conv(tp.ay, nullptr, w->aout_w, w->aout_b, tp.zeros, tp.hatt, h, B, H, W, dim, 0, dim, 9, BSI_CONV_BIAS_RESID_F32, stream, part(1)));
+    TRY(attention(h, hp, w->agn_w, w->agn_b, w->aqkv_w, w->aqkv_b, w->aout_w, w->aout_b, cfg->heads, tp.agn, tp.qkv, tp.ay, tp.lse,
+                  tp.gnstats + (size_t)d.nblocks * B * 64, tp.hatt, 1));
     TRY(resblock(L + 1, tp.hatt, 1, nullptr, 0));
     h = block_tape(tp, d, L + 1).out;
     hp = 2 + L + 1;
@@ -349,6 +404,39 @@ extern "C" int bsi_unet_backward(const bsi_unet_config* cfg, const bsi_unet_weig
                                           rg.gn_b, ws.g, d.HW <= 1024 ? tp.gnstats + (size_t)blk * B * 64 : nullptr, ws.gnpart, stream);
     };
 
+    // Residual(GroupNorm -> Attention2D) backward (attention.py:32-41): dOut -> out = dOut + d(x) through the stage; x = its input.
+    // Ends like resblock_bwd: ws.g holds the bf16 copy of `out`.
+    auto attention_bwd = [&](const float* dOut, const float* x, const char* agn, const char* qkv, const char* ay, const float* lse, int heads,
+                             const float* gw, const float* gb, const void* qkv_wT, const void* out_wT, float* g_gn_w, float* g_gn_b,
+                             float* g_qkv_w, float* g_qkv_b, float* g_out_w, float* g_out_b, const float* stats, float* out) -> int {
+        if (!g_ready) TRY(bsi_silu_bwd_bf16(dOut, nullptr, (size_t)M * dim, ws.g, stream));
+        TRY(bsi_conv_wgrad_conv2d_nhwc_bf16(ws.g, dim, ay, nullptr, tp.zeros, B, H, W, dim, dim, 0, dim, 9, g_out_w, nullptr, g_out_b, ws.wg,
+                                            stream));
+        TRY(conv(ws.g, nullptr, out_wT, nullptr, tp.zeros, ws.dy, nullptr, B, H, W, dim, 0, dim, 9, BSI_CONV_BIAS_BF16, stream));
+        TRY(bsi_attention_bwd_long(qkv, 3 * dim, ay, ws.dy, dim, lse, B, d.HW, heads, dim / heads, ws.dqkv, 3 * dim, stream));
+        TRY(bsi_conv_wgrad_conv2d_nhwc_bf16(ws.dqkv, 3 * dim, agn, nullptr, tp.zeros, B, H, W, dim, dim, 0, 3 * dim, 9, g_qkv_w, nullptr,
+                                            g_qkv_b, ws.wg, stream));
+        TRY(conv(ws.dqkv, nullptr, qkv_wT, nullptr, tp.zeros, ws.da, nullptr, B, H, W, 3 * dim, 0, dim, 9, BSI_CONV_BIAS_BF16, stream));
+        TRY(bsi_groupnorm_bwd_cast_det(ws.da, x, dim, nullptr, 0, B, d.HW, gw, gb, 1e-5f, 0, dOut, nullptr, out, nullptr, g_gn_w, g_gn_b, ws.g,
+                                       d.HW <= 1024 ? stats : nullptr, ws.gnpart, stream));
+        g_ready = true;
+        return BSI_OK;
+    };
+    // a residual block with its per-block attention stage (block_heads > 0): the stage's reverse first, into ws.datt
+    auto block_bwd = [&](int blk, const float* dOut, const float* x1, const float* x2, const float* add_b, float* out1, float* out2) -> int {
+        if (cfg->block_heads > 0) {
+            const bsi_unet_resblock_weights& rb = w->blocks[blk];
+            const bsi_unet_resblock_weights_t& rT = wT->blocks[blk];
+            const bsi_unet_resblock_grads& rg = g->blocks[blk];
+            const AttnTape at = attn_tape(tp, d, blk);
+            TRY(attention_bwd(dOut, at.in, at.agn, at.qkv, at.ay, at.lse, cfg->block_heads, rb.agn_w, rb.agn_b, rT.aqkv_wT, rT.aout_wT, rg.agn_w,
+                              rg.agn_b, rg.aqkv_w, rg.aqkv_b, rg.aout_w, rg.aout_b, tp.gnstats + (size_t)(d.nblocks + 1 + blk) * B * 64,
+                              ws.datt));
+            dOut = ws.datt;
+        }
+        return resblock_bwd(blk, dOut, x1, x2, add_b, out1, out2);
+    };
+
     int cur = 0;
     const float* hlast = block_tape(tp, d, d.nblocks - 1).out;
     TRY(bsi_unet_decode_bwd_det(g_out, c_out, 1, hlast, B, d.HW, dim, w->dec_w, cfg->C, ws.dcur[cur], g->dec_w, g->dec_b, ws.decparts, stream));
@@ -356,34 +444,22 @@ extern "C" int bsi_unet_backward(const bsi_unet_config* cfg, const bsi_unet_weig
         const int blk = L + 2 + i;
         const float* x1 = i == 0 ? block_tape(tp, d, L + 1).out : block_tape(tp, d, blk - 1).out;
         const float* x2 = block_tape(tp, d, L - 1 - i).out;
-        TRY(resblock_bwd(blk, ws.dcur[cur], x1, x2, nullptr, ws.dcur[cur ^ 1], dskip(L - 1 - i)));
+        TRY(block_bwd(blk, ws.dcur[cur], x1, x2, nullptr, ws.dcur[cur ^ 1], dskip(L - 1 - i)));
         cur ^= 1;
     }
-    TRY(resblock_bwd(L + 1, ws.dcur[cur], tp.hatt, nullptr, nullptr, ws.dcur[cur ^ 1], nullptr));
+    TRY(block_bwd(L + 1, ws.dcur[cur], tp.hatt, nullptr, nullptr, ws.dcur[cur ^ 1], nullptr));
     cur ^= 1;
-    {   // Residual(GroupNorm -> Attention2D) (vdm_unet.py:83-87)
-        const float* dOut = ws.dcur[cur];
-        const float* hin = block_tape(tp, d, L).out;
-        if (!g_ready) TRY(bsi_silu_bwd_bf16(dOut, nullptr, (size_t)M * dim, ws.g, stream));
-        TRY(bsi_conv_wgrad_conv2d_nhwc_bf16(ws.g, dim, tp.ay, nullptr, tp.zeros, B, H, W, dim, dim, 0, dim, 9, g->aout_w, nullptr, g->aout_b, ws.wg,
-                                            stream));
-        TRY(conv(ws.g, nullptr, wT->aout_wT, nullptr, tp.zeros, ws.dy, nullptr, B, H, W, dim, 0, dim, 9, BSI_CONV_BIAS_BF16, stream));
-        TRY(bsi_attention_bwd_long(tp.qkv, 3 * dim, tp.ay, ws.dy, dim, tp.lse, B, d.HW, cfg->heads, d.dh, ws.dqkv, 3 * dim, stream));
-        TRY(bsi_conv_wgrad_conv2d_nhwc_bf16(ws.dqkv, 3 * dim, tp.agn, nullptr, tp.zeros, B, H, W, dim, dim, 0, 3 * dim, 9, g->aqkv_w, nullptr,
-                                            g->aqkv_b, ws.wg, stream));
-        TRY(conv(ws.dqkv, nullptr, wT->aqkv_wT, nullptr, tp.zeros, ws.da, nullptr, B, H, W, 3 * dim, 0, dim, 9, BSI_CONV_BIAS_BF16, stream));
-        TRY(bsi_groupnorm_bwd_cast_det(ws.da, hin, dim, nullptr, 0, B, d.HW, w->agn_w, w->agn_b, 1e-5f, 0, dOut, nullptr, ws.dcur[cur ^ 1],
-                                       nullptr, g->agn_w, g->agn_b, ws.g, d.HW <= 1024 ? tp.gnstats + (size_t)d.nblocks * B * 64 : nullptr,
-                                       ws.gnpart, stream));
-        g_ready = true;
-        cur ^= 1;
-    }
+    // Residual(GroupNorm -> Attention2D) of the centre (vdm_unet.py:83-87)
+    TRY(attention_bwd(ws.dcur[cur], block_tape(tp, d, L).out, tp.agn, tp.qkv, tp.ay, tp.lse, cfg->heads, w->agn_w, w->agn_b, wT->aqkv_wT,
+                      wT->aout_wT, g->agn_w, g->agn_b, g->aqkv_w, g->aqkv_b, g->aout_w, g->aout_b, tp.gnstats + (size_t)d.nblocks * B * 64,
+                      ws.dcur[cur ^ 1]));
+    cur ^= 1;
     // centre block 0 and the down path: the output of down block i is also the skip tensor of up block L-1-i
-    TRY(resblock_bwd(L, ws.dcur[cur], L > 0 ? block_tape(tp, d, L - 1).out : tp.henc, nullptr, L > 0 ? dskip(L - 1) : nullptr,
+    TRY(block_bwd(L, ws.dcur[cur], L > 0 ? block_tape(tp, d, L - 1).out : tp.henc, nullptr, L > 0 ? dskip(L - 1) : nullptr,
                      ws.dcur[cur ^ 1], nullptr));
     cur ^= 1;
     for (int i = L - 1; i >= 0; --i) {
-        TRY(resblock_bwd(i, ws.dcur[cur], i > 0 ? block_tape(tp, d, i - 1).out : tp.henc, nullptr, i > 0 ? dskip(i - 1) : nullptr,
+        TRY(block_bwd(i, ws.dcur[cur], i > 0 ? block_tape(tp, d, i - 1).out : tp.henc, nullptr, i > 0 ? dskip(i - 1) : nullptr,
                          ws.dcur[cur ^ 1], nullptr));
         cur ^= 1;
     }

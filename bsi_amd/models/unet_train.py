@@ -46,6 +46,11 @@ def _grad_plan(model, cfg, flat, key):
         arr[i].conv2_w = views[pfx + f"layers.{last}.weight"].data_ptr()
         arr[i].conv2_b = views[pfx + f"layers.{last}.bias"].data_ptr()
         arr[i].skip_w = views[pfx + "skip.weight"].data_ptr() if has_skip else None
+        if rb.attention:
+            apf = pfx + "res_attention.fn."
+            arr[i].agn_w, arr[i].agn_b = views[apf + "0.weight"].data_ptr(), views[apf + "0.bias"].data_ptr()
+            arr[i].aqkv_w, arr[i].aqkv_b = views[apf + "1.to_qkv.weight"].data_ptr(), views[apf + "1.to_qkv.bias"].data_ptr()
+            arr[i].aout_w, arr[i].aout_b = views[apf + "1.to_out.weight"].data_ptr(), views[apf + "1.to_out.bias"].data_ptr()
         if has_skip:
             skip_bias.append((pfx + "skip.bias", pfx + f"layers.{last}.bias"))
     F = len(names) * 2 * dim
@@ -129,6 +134,9 @@ def _build_plan_t(model, skey):
         arr[i].conv1_wT = conv_t(rb.layers[2])
         arr[i].conv2_wT = conv_t(rb.layers[-1])
         arr[i].skip_wT = conv_t(rb.skip) if isinstance(rb.skip, nn.Conv2d) else None
+        if rb.attention:
+            arr[i].aqkv_wT = conv_t(rb.res_attention.fn[1].to_qkv)
+            arr[i].aout_wT = conv_t(rb.res_attention.fn[1].to_out)
     wt = N.UNetWeightsT()
     wt.blocks = C.cast(arr, C.POINTER(N.UNetResBlockWeightsT))
     att = model.u_net.center_block[1].fn[1]

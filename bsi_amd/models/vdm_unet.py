@@ -41,9 +41,6 @@ class ResidualBlock(nn.Module):
     def __init__(self, dim_in, dim_out, *, c_dim: int, ActFn, Norm, dropout, attention: bool = True,
                  padding_mode: str = "zeros"):
         super().__init__()
-        if attention:
-            raise NotImplementedError("bsi_amd.ResidualBlock: downsampling_attention=True is not on the native path "
-                                      "(no experiment of the reference uses it)")
         self.project_onto_scale_shift = nn.Linear(c_dim, dim_out * 2, 1)
         self.skip = nn.Conv2d(dim_in, dim_out, 1) if dim_in != dim_out else nn.Identity()
         self.layers = nn.Sequential(
@@ -51,7 +48,9 @@ class ResidualBlock(nn.Module):
             *([nn.Dropout(dropout)] if dropout is not None else []),
             nn.Conv2d(dim_out, dim_out, 3, padding=1, padding_mode=padding_mode))
         self.attention = attention
-        self.res_attention = nn.Identity()
+        # residual_block.py:50-58: Attention2D keeps its default 4 heads (head dim 32 at dim 128)
+        self.res_attention = (Residual(nn.Sequential(Norm(dim_out), Attention2D(dim_out, padding_mode=padding_mode)))
+                              if attention else nn.Identity())
 
 
 class SimplifiedUNet(nn.Module):
@@ -80,6 +79,10 @@ class DenoisingVDMUNet(nn.Module):
         if actfn != "silu" or padding_mode != "zeros":
             raise NotImplementedError("bsi_amd.DenoisingVDMUNet: the native kernels implement actfn='silu' and "
                                       "padding_mode='zeros' (the reference's configuration)")
+        if downsampling_attention and dim != 128:
+            raise NotImplementedError(f"bsi_amd.DenoisingVDMUNet: downsampling_attention=True needs dim=128 (the per-block "
+                                      f"Attention2D has 4 heads; dim={dim} gives head dim {dim // 4}, and the native attention "
+                                      "kernels implement head dims 32, 64 and 128)")
         n_channels = data_shape[0]
         in_features = out_features = n_channels
         if fourier_features is not None:
@@ -104,7 +107,8 @@ class DenoisingVDMUNet(nn.Module):
                                                                              padding_mode=padding_mode))),
                                residual_block(dim, dim, c_dim))
         self.u_net = SimplifiedUNet(down, up, center)
-        self._cfg_args = dict(dim=dim, levels=levels, heads=n_attention_heads, c_dim=c_dim)
+        self._cfg_args = dict(dim=dim, levels=levels, heads=n_attention_heads, c_dim=c_dim,
+                              block_heads=4 if downsampling_attention else 0)
         self._dropout = dropout
         self._pack = None
         self._pack_key = None
@@ -120,7 +124,7 @@ class DenoisingVDMUNet(nn.Module):
         ff = self.fourier_features
         a = self._cfg_args
         return N.UNetConfig(Cc, H, W, a["dim"], a["levels"], a["heads"], ff.n_min if ff is not None else 1,
-                            ff.n_max if ff is not None else 0, self.pos_emb.size, a["c_dim"])
+                            ff.n_max if ff is not None else 0, self.pos_emb.size, a["c_dim"], a["block_heads"])
 
     _NATIVE_CACHES = ("_pack", "_pack_key", "_pack_t", "_pack_t_key", "_plan", "_plan_t", "_plan_g", "_ws", "_last_flat_grad", "_grad_buffer")
 
@@ -233,6 +237,11 @@ class DenoisingVDMUNet(nn.Module):
             arr[i].conv1_w, arr[i].conv1_b = conv_pack(rb.layers[2]), f32(rb.layers[2].bias)
             arr[i].conv2_w = conv_pack(conv2, extra=rb.skip if has_skip else None)
             arr[i].conv2_b = b2_dst[skips.index(i)].data_ptr() if has_skip else f32(conv2.bias)
+            if rb.attention:  # res_attention.fn = (GroupNorm, Attention2D)
+                ra = rb.res_attention.fn
+                arr[i].agn_w, arr[i].agn_b = f32(ra[0].weight), f32(ra[0].bias)
+                arr[i].aqkv_w, arr[i].aqkv_b = conv_pack(ra[1].to_qkv), f32(ra[1].to_qkv.bias)
+                arr[i].aout_w, arr[i].aout_b = conv_pack(ra[1].to_out), f32(ra[1].to_out.bias)
         w = N.UNetWeights()
         w.enc_w, w.enc_b = conv_pack(self.encode, cin_pad=lib.bsi_unet_cin_pad(C.byref(cfg))), f32(self.encode.bias)
         w.dec_w, w.dec_b = f32(self.decode.weight.detach().reshape(self.decode.weight.shape[0], -1)), f32(self.decode.bias)

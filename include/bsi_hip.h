@@ -297,11 +297,11 @@ int bsi_resid2_ln_modulate(float* x, int M, int d, float eps, const void* delta0
 
 /* dit.py:39-46 / attention.py:34-40: softmax(q k^T / sqrt(dh)) v per (batch, head), non-causal.
  * qkv: bf16 [B, tokens, 3, heads, dh] (row stride ld_qkv elements); out: bf16 [B, tokens, heads*dh]
- * (row stride ld_out).  dh in {64, 128}; tokens % 64 == 0. */
+ * (row stride ld_out).  dh in {32, 64, 128} (32: the VDM-UNet's per-block Attention2D, 4 heads at dim 128); tokens % 64 == 0. */
 int bsi_attention_fwd(const void* qkv, int ld_qkv, int B, int tokens, int heads, int dh, void* out, int ld_out,
                       bsi_stream_t stream);
 
-/* As bsi_attention_fwd, additionally saving lse[b,h,q] = log sum_k exp(q.k/sqrt(dh)) (fp32 [B,heads,tokens]). */
+/* As bsi_attention_fwd (same dh and tokens), additionally saving lse[b,h,q] = log sum_k exp(q.k/sqrt(dh)) (fp32 [B,heads,tokens]). */
 int bsi_attention_fwd_lse(const void* qkv, int ld_qkv, int B, int tokens, int heads, int dh, void* out, int ld_out,
                           float* lse, bsi_stream_t stream);
 /* Backward of the attention (autograd of dit.py:43-44): dqkv (bf16, layout of qkv) from qkv, the forward output
@@ -309,7 +309,8 @@ int bsi_attention_fwd_lse(const void* qkv, int ld_qkv, int B, int tokens, int he
 int bsi_attention_bwd(const void* qkv, int ld_qkv, const void* out, const void* dout, int ld_o, const float* lse,
                       int B, int tokens, int heads, int dh, void* dqkv, int ld_dqkv, bsi_stream_t stream);
 /* Same contract for long sequences / wide heads (UNet centre attention, attention.py:18,38: 1024 positions, dh 128):
- * the other side of each pass is streamed through LDS; tokens % 64 == 0, dh 64 or 128, no dropout. */
+ * the other side of each pass is streamed through LDS; tokens % 64 == 0, dh 32, 64 or 128 (32: the per-block attention of
+ * residual_block.py:50-64), no dropout. */
 int bsi_attention_bwd_long(const void* qkv, int ld_qkv, const void* out, const void* dout, int ld_o, const float* lse,
                            int B, int tokens, int heads, int dh, void* dqkv, int ld_dqkv, bsi_stream_t stream);
 
@@ -523,11 +524,17 @@ typedef struct bsi_unet_config {
     int ff_nmin, ff_nmax;
     int emb_size;     /* pos_emb.size (32) */
     int c_dim;        /* pos_emb.size * pos_emb_mult (128) */
+    int block_heads;  /* downsampling_attention (residual_block.py:50-64): Residual(GroupNorm -> Attention2D(heads=block_heads)) after
+                       * EVERY residual block; 0 = none.  Head dim dim/block_heads must be 32 (dim 128, 4 heads). */
 } bsi_unet_config;
 typedef struct bsi_unet_resblock_weights {
     const float *gn_w, *gn_b;                  /* layers.0: GroupNorm(32, Cin) */
     const void* conv1_w; const float* conv1_b; /* layers.2: bf16 [dim][9*Cin] (bsi_conv_weight_pack) */
     const void* conv2_w; const float* conv2_b; /* layers.5|6 (+ skip 1x1 appended as K columns, its bias added): bf16 [dim][9*dim (+2*dim)] */
+    /* res_attention (block_heads > 0, else NULL): fn.0 GroupNorm(32, dim), fn.1.to_qkv bf16 [3*dim][9*dim], fn.1.to_out bf16 [dim][9*dim] */
+    const float *agn_w, *agn_b;
+    const void* aqkv_w; const float* aqkv_b;
+    const void* aout_w; const float* aout_b;
 } bsi_unet_resblock_weights;
 typedef struct bsi_unet_weights {
     const void* enc_w; const float* enc_b;     /* encode: bf16 [dim][9*cin_pad] */
@@ -559,6 +566,8 @@ typedef struct bsi_unet_resblock_weights_t { /* bf16 shadows for the input-gradi
     const void* conv1_wT; /* [Cin][9*dim]  bsi_conv_weight_pack_t(layers.2.weight) */
     const void* conv2_wT; /* [dim][9*dim]  bsi_conv_weight_pack_t(layers.5|6.weight) */
     const void* skip_wT;  /* up blocks: [2*dim][dim] = bsi_conv_weight_pack_t(skip.weight, taps 1); else NULL */
+    const void* aqkv_wT;  /* block_heads > 0: res_attention.fn.1.to_qkv [dim][9*3*dim]; else NULL */
+    const void* aout_wT;  /* block_heads > 0: res_attention.fn.1.to_out [dim][9*dim]; else NULL */
 } bsi_unet_resblock_weights_t;
 typedef struct bsi_unet_weights_t {
     const bsi_unet_resblock_weights_t* blocks; /* host array [2*levels+2], order of bsi_unet_weights.blocks */
@@ -572,6 +581,9 @@ typedef struct bsi_unet_resblock_grads { /* fp32, WRITTEN; conv weights in the t
     float* conv1_w; float* conv1_b; /* [dim][Cin][3][3] */
     float* conv2_w; float* conv2_b; /* [dim][dim][3][3]; conv2_b is also the skip conv's bias gradient */
     float* skip_w;                  /* up blocks: [dim][2*dim] (the folded 1x1 skip convolution), else NULL */
+    float *agn_w, *agn_b;           /* block_heads > 0: res_attention (layouts of bsi_unet_grads.agn_w ..); else NULL */
+    float* aqkv_w; float* aqkv_b;
+    float* aout_w; float* aout_b;
 } bsi_unet_resblock_grads;
 typedef struct bsi_unet_grads {
     float* enc_w; float* enc_b;         /* [dim][C + Fourier channels][3][3] (unpadded) */

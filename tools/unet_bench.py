@@ -1,6 +1,10 @@
 #!/usr/bin/env python
 """Secondary benchmark: images/s of BSI.sample (k=128) with the VDM-UNet of config/experiment/cifar10-vdm.yaml
-(dim 128, levels 32, 1 attention head) on one GPU; 53.47 GFLOP per evaluation per image."""
+(dim 128, levels 32, 1 attention head) on one GPU; 53.47 GFLOP per evaluation per image.
+--downsampling-attention: the same UNet with Residual(GroupNorm -> Attention2D) after every residual block (4 heads of 32
+channels; the GFLOP figure then counts only the default UNet's work).  --train N: also time N train_loss backward steps (B images).
+"""
+import argparse
 import os
 import sys
 import time
@@ -13,12 +17,17 @@ from bsi_amd.models.pos_emb import NyquistPositionalEmbedding  # noqa: E402
 from bsi_amd.models.vdm_unet import DenoisingVDMUNet  # noqa: E402
 from bsi_amd.nn import FourierFeatures  # noqa: E402
 
+ap = argparse.ArgumentParser()
+ap.add_argument("--downsampling-attention", action="store_true")
+ap.add_argument("--train", type=int, default=0, metavar="N")
+args = ap.parse_args()
 B = int(os.environ.get("B", "256"))
 K = int(os.environ.get("K", "128"))
 dev = torch.device("cuda", 0)
 shape = (3, 32, 32)
 torch.manual_seed(0)
 m = DenoisingVDMUNet(shape, NyquistPositionalEmbedding(32, 100), "silu", 128, 32, 4, n_attention_heads=1, dropout=0.1,
+                     downsampling_attention=args.downsampling_attention,
                      fourier_features=FourierFeatures(n_min=6, n_max=8)).to(dev).eval()
 bsi = BSI(m, data_shape=shape, lambda_0=1e-2, alpha_M=1e6, alpha_R=2e6, k=K, preconditioning="edm",
           discretization=Discretization.image_8bit()).to(dev)
@@ -31,4 +40,16 @@ with torch.no_grad():
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
 assert torch.isfinite(out).all()
-print(f"UNet BSI.sample k={K} B={B}: {B / dt:.2f} images/s, {B / dt * (K + 1) * 53.47 / 1e3:.0f} model TFLOP/s")
+tag = " downsampling_attention" if args.downsampling_attention else ""
+print(f"UNet{tag} BSI.sample k={K} B={B}: {B / dt:.2f} images/s, {B / dt * (K + 1) * 53.47 / 1e3:.0f} model TFLOP/s")
+if args.train:
+    m.train()
+    x = torch.rand((B, *shape), device=dev) * 2 - 1
+    bsi.train_loss(x, g).mean().backward()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(args.train):
+        bsi.train_loss(x, g).mean().backward()
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    print(f"UNet{tag} train_loss backward B={B}: {args.train / dt:.3f} steps/s")
