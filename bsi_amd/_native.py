@@ -53,10 +53,13 @@ class ConvArgs(C.Structure):
                 ("out", C.c_void_p), ("film", C.c_void_p), ("resid", C.c_void_p), ("film_rows", C.c_int),
                 ("film_stride", C.c_int), ("B", C.c_int), ("H", C.c_int), ("W", C.c_int), ("Cin", C.c_int),
                 ("Cin2", C.c_int), ("Cout", C.c_int), ("taps", C.c_int), ("ldo", C.c_int), ("epilogue", C.c_int),
-                ("gn_partial", C.c_void_p)]
+                ("gn_partial", C.c_void_p), ("act", C.c_int)]
 
 
 CONV_BIAS_BF16, CONV_FILM_SILU_BF16, CONV_BIAS_RESID_F32 = range(3)
+# activation codes BSI_ACT_* (include/bsi_hip.h): the UNet's actfn names (bsi/models/utils.py:4-12)
+ACT_NONE, ACT_SILU, ACT_GELU, ACT_RELU, ACT_SOFTPLUS, ACT_TANH = range(6)
+ACT_CODES = {"silu": ACT_SILU, "gelu": ACT_GELU, "relu": ACT_RELU, "softplus": ACT_SOFTPLUS, "tanh": ACT_TANH}
 
 
 class ConvPackDesc(C.Structure):
@@ -78,7 +81,8 @@ class UNetWeights(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("enc_w", "enc_b", "dec_w", "dec_b", "pe_scale", "pe_bias", "pm1_w", "pm1_b", "pm3_w",
                                           "pm3_b", "film_w", "film_b")] + \
                [("blocks", C.POINTER(UNetResBlockWeights))] + \
-               [(k, C.c_void_p) for k in ("agn_w", "agn_b", "aqkv_w", "aqkv_b", "aout_w", "aout_b")]
+               [(k, C.c_void_p) for k in ("agn_w", "agn_b", "aqkv_w", "aqkv_b", "aout_w", "aout_b")] + \
+               [("actfn", C.c_int)]
 
 
 class UNetResBlockWeightsT(C.Structure):
@@ -240,6 +244,10 @@ _PROTOS = {
     "bsi_groupnorm_bwd_cast_nhwc": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _vp, _vp, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "bsi_film_silu": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _f, C.c_ulonglong, C.c_uint, _vp, _vp]),
     "bsi_film_silu_bwd": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i, _f, C.c_ulonglong, C.c_uint, _vp, _vp, _i, _vp]),
+    "bsi_film_act": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _i, _f, C.c_ulonglong, C.c_uint, _vp, _vp]),
+    "bsi_film_act_bwd": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i, _i, _f, C.c_ulonglong, C.c_uint, _vp, _vp, _i, _vp]),
+    "bsi_act_bf16": (_i, [_vp, _sz, _i, _vp, _vp]),
+    "bsi_act_bwd_bf16": (_i, [_vp, _vp, _sz, _i, _vp, _vp]),
     "bsi_unet_decode_bwd": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp]),
     "bsi_unet_decode": (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp]),
     "bsi_unet_cin_pad": (_i, [C.POINTER(UNetConfig)]),

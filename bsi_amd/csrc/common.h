@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/bsi_hip.h"
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
@@ -228,6 +230,73 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 __device__ __forceinline__ float silu_f(float x) {
     return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * x));
+}
+__device__ __forceinline__ float silu_grad_f(float z) {
+    const float s = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * z));
+    return s * (1.0f + z * (1.0f - s));
+}
+
+// nn.Softplus() = log1p(exp(x)), x above 20: x.  Written as max(x, 0) + log1p(exp(-|x|)): above 20, exp(-x) < 2.1e-9 is below half an
+// ulp of x, so the sum is x as torch returns it.  Branch-free on purpose: the conditional form and log1pf compile to divergent
+// branches, which the convolution epilogues (uniform tile index pinned to scalar registers) cannot hold.  log1p(u), u in (0, 1], as
+// log(w) * u / (w - 1) with w = 1 + u (exact to a few ulp: the rounding of w cancels), u itself where w rounds to 1.
+__device__ __forceinline__ float softplus_f(float x) {
+    const float u = expf(-fabsf(x));
+    const float w = 1.0f + u;
+    const float l = w == 1.0f ? u : logf(w) * (u / (w - 1.0f));
+    return fmaxf(x, 0.0f) + l;
+}
+
+// The UNet's ActFn (BSI_ACT_* of include/bsi_hip.h; bsi/models/utils.py:4-12 of the reference) as torch's defaults compute it,
+// value and derivative at the PRE-activation x.  GELU is the exact erf form of nn.GELU() (not gelu_tanh_f, the DiT's
+// approximate="tanh"); Softplus has beta 1 and threshold 20 (x > 20: x and derivative 1); ReLU' is 0 at x = 0.
+template <int ACT>
+__device__ __forceinline__ float act_f(float x) {
+    static_assert(ACT >= BSI_ACT_NONE && ACT <= BSI_ACT_TANH, "activation code");
+    if constexpr (ACT == BSI_ACT_SILU) return silu_f(x);
+    else if constexpr (ACT == BSI_ACT_GELU) return 0.5f * x * (1.0f + erff(x * 0.70710678118654752f));
+    else if constexpr (ACT == BSI_ACT_RELU) return x > 0.0f ? x : 0.0f;
+    else if constexpr (ACT == BSI_ACT_SOFTPLUS) return softplus_f(x);
+    else if constexpr (ACT == BSI_ACT_TANH) return tanhf(x);
+    else return x;
+}
+template <int ACT>
+__device__ __forceinline__ float act_grad_f(float x) {
+    static_assert(ACT >= BSI_ACT_NONE && ACT <= BSI_ACT_TANH, "activation code");
+    if constexpr (ACT == BSI_ACT_SILU) return silu_grad_f(x);
+    else if constexpr (ACT == BSI_ACT_GELU)  // Phi(x) + x phi(x)
+        return 0.5f * (1.0f + erff(x * 0.70710678118654752f)) + x * 0.39894228040143268f * expf(-0.5f * x * x);
+    else if constexpr (ACT == BSI_ACT_RELU) return x > 0.0f ? 1.0f : 0.0f;
+    else if constexpr (ACT == BSI_ACT_SOFTPLUS) return x > 20.0f ? 1.0f : 1.0f / (1.0f + expf(-x));
+    else if constexpr (ACT == BSI_ACT_TANH) { const float t = tanhf(x); return 1.0f - t * t; }
+    else return 1.0f;
+}
+// Kernels that took a run-time `silu` flag (GroupNorm forward and backward) keep it in the instantiation ACT_FLAG (flag 0 = none,
+// 1 = SiLU: the code they always had); the other activations get instantiations of their own, which ignore the flag.
+constexpr int ACT_FLAG = -1;
+template <class F>
+inline int bsi_with_act_flag(int act, const char* who, F&& f) {
+    switch (act) {
+        case BSI_ACT_NONE: case BSI_ACT_SILU: return f(std::integral_constant<int, ACT_FLAG>{});
+        case BSI_ACT_GELU: return f(std::integral_constant<int, BSI_ACT_GELU>{});
+        case BSI_ACT_RELU: return f(std::integral_constant<int, BSI_ACT_RELU>{});
+        case BSI_ACT_SOFTPLUS: return f(std::integral_constant<int, BSI_ACT_SOFTPLUS>{});
+        case BSI_ACT_TANH: return f(std::integral_constant<int, BSI_ACT_TANH>{});
+        default: bsi_set_error("%s: unknown activation code %d (BSI_ACT_NONE .. BSI_ACT_TANH)", who, act); return BSI_EINVAL;
+    }
+}
+// Host side: run f(std::integral_constant<int, ACT>{}) for a run-time activation code; an unknown code is BSI_EINVAL.
+template <class F>
+inline int bsi_with_act(int act, const char* who, F&& f) {
+    switch (act) {
+        case BSI_ACT_NONE: return f(std::integral_constant<int, BSI_ACT_NONE>{});
+        case BSI_ACT_SILU: return f(std::integral_constant<int, BSI_ACT_SILU>{});
+        case BSI_ACT_GELU: return f(std::integral_constant<int, BSI_ACT_GELU>{});
+        case BSI_ACT_RELU: return f(std::integral_constant<int, BSI_ACT_RELU>{});
+        case BSI_ACT_SOFTPLUS: return f(std::integral_constant<int, BSI_ACT_SOFTPLUS>{});
+        case BSI_ACT_TANH: return f(std::integral_constant<int, BSI_ACT_TANH>{});
+        default: bsi_set_error("%s: unknown activation code %d (BSI_ACT_NONE .. BSI_ACT_TANH)", who, act); return BSI_EINVAL;
+    }
 }
 
 // Counter-based dropout (training only): element `idx` of site `seed` is kept iff hash(seed, idx) >= p * 2^32.

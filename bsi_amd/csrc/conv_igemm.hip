@@ -41,7 +41,8 @@ constexpr unsigned OOB_OFFSET = 0xFFFFFF00u;   // buffer offset beyond num_recor
 constexpr unsigned BUF_RECORDS = 0x80000000u;  // every valid offset is below 2 GB (checked by the launcher)
 
 // FILM_SILU_BF16: every wave's 128 rows lie in one image (H*W % 128 == 0, coefficients once per tile, applied in place);
-// FILM_ROWS_SILU_BF16: any image size, coefficients looked up per row (ring kernel only)
+// FILM_ROWS_SILU_BF16: any image size, coefficients looked up per row (ring kernel only).  The FiLM epilogues apply the kernels'
+// template parameter ACT (BSI_ACT_*, bsi_conv_args.act; SiLU by default), which the other epilogues ignore.
 enum { CEPI_BIAS_BF16 = 0, CEPI_FILM_SILU_BF16 = 1, CEPI_BIAS_RESID_F32 = 2, CEPI_BIAS_RESID_F32_GN = 3, CEPI_FILM_ROWS_SILU_BF16 = 4 };
 
 // Padding code of a pixel: which of the four image borders it touches.  A tap (dy, dx) reads outside the image exactly
@@ -69,12 +70,12 @@ __device__ __forceinline__ void store_rows_dpp(__bf16* out, int ldo, int M, int 
     if (m_even + 1 < M) __builtin_nontemporal_store(st_odd, reinterpret_cast<u32x4*>(dst + ldo));
 }
 
-// FiLM + SiLU (residual_block.py:21-24,44-46: addcmul(shift, scale + 1, y), then SiLU) IN PLACE on a wave's accumulators when its
+// FiLM + ActFn (residual_block.py:21-24,44-46: addcmul(shift, scale + 1, y), then ActFn = act_f<ACT>) IN PLACE on a wave's accumulators when its
 // 128 rows lie in one image (H*W % 128 == 0): the (scale, shift) of 4 columns are loaded, applied to the 8 rows, and dropped
 // before the next 4 -- nothing but the accumulators stays live (the coefficient arrays of the earlier form cost 160 spilled
 // registers in the ring kernel, some of them inside the K loop).
-template <int TM>
-__device__ __forceinline__ void film_silu_inplace(const ConvParams& p, f32x4 (&acc)[4][TM], int mw0, int nb, int HW) {
+template <int ACT, int TM>
+__device__ __forceinline__ void film_act_inplace(const ConvParams& p, f32x4 (&acc)[4][TM], int mw0, int nb, int HW) {
     const int m0w = mw0 < p.M ? mw0 : p.M - 1;
     asm volatile("" : "+v"(nb));  // keeps the lane's column offsets out of loop-invariant code motion (they would live across the K loop)
     const float* fr = p.film + (size_t)((m0w / HW) % p.film_rows) * p.film_stride + nb;
@@ -87,7 +88,7 @@ __device__ __forceinline__ void film_silu_inplace(const ConvParams& p, f32x4 (&a
 #pragma unroll
         for (int j = 0; j < TM; ++j) {
 #pragma unroll
-            for (int r = 0; r < 4; ++r) acc[i][j][r] = silu_f(__fmaf_rn(sc[r], acc[i][j][r], sh[r]));
+            for (int r = 0; r < 4; ++r) acc[i][j][r] = act_f<ACT>(__fmaf_rn(sc[r], acc[i][j][r], sh[r]));
             if (j & 1) __builtin_amdgcn_sched_barrier(0);  // a few independent exp / rcp chains at a time, not all 128
         }
     }
@@ -209,7 +210,7 @@ __device__ __forceinline__ void store_f32_rows(const ConvParams& p, f32x4 (&acc)
     }
 }
 
-template <int EPI>
+template <int EPI, int ACT = BSI_ACT_SILU>
 __global__ __launch_bounds__(512) void conv_ring_kernel(const ConvParams p) {
     constexpr int TM = 8, NW = 8;
     constexpr bool BF16_OUT = (EPI < CEPI_BIAS_RESID_F32 || EPI == CEPI_FILM_ROWS_SILU_BF16);
@@ -336,7 +337,7 @@ __global__ __launch_bounds__(512) void conv_ring_kernel(const ConvParams p) {
         if (nb0 >= p.N || (BSI_ABL(p.abl, 4))) return;  // wave-uniform: the lane-group exchanges below need every lane
         if constexpr (BF16_OUT) {
             if (nb >= p.N) return;
-            if constexpr (EPI == CEPI_FILM_SILU_BF16) film_silu_inplace(p, acc, mw0, nb, HW);
+            if constexpr (EPI == CEPI_FILM_SILU_BF16) film_act_inplace<ACT>(p, acc, mw0, nb, HW);
 #pragma unroll
             for (int j = 0; j < TM; ++j) {
                 float v[16];
@@ -345,7 +346,7 @@ __global__ __launch_bounds__(512) void conv_ring_kernel(const ConvParams p) {
 #pragma unroll
                     for (int r = 0; r < 4; ++r) v[4 * i + r] = acc[i][j][r];
                 if constexpr (EPI == CEPI_FILM_ROWS_SILU_BF16) {
-                    // y*(scale+1)+shift (FeatureModulation, residual_block.py:21-24: addcmul(shift, scale+1, y)), then SiLU
+                    // y*(scale+1)+shift (FeatureModulation, residual_block.py:21-24: addcmul(shift, scale+1, y)), then ActFn
                     int m = mw0 + 16 * j + rho;
                     m = m < p.M ? m : p.M - 1;
                     const float* fr = p.film + (size_t)((m / HW) % p.film_rows) * p.film_stride;
@@ -354,7 +355,7 @@ __global__ __launch_bounds__(512) void conv_ring_kernel(const ConvParams p) {
                         const f32x4 sc = *reinterpret_cast<const f32x4*>(fr + nb + e);
                         const f32x4 sh = *reinterpret_cast<const f32x4*>(fr + p.N + nb + e);
 #pragma unroll
-                        for (int r = 0; r < 4; ++r) v[e + r] = silu_f(__fmaf_rn(sc[r] + 1.0f, v[e + r], sh[r]));
+                        for (int r = 0; r < 4; ++r) v[e + r] = act_f<ACT>(__fmaf_rn(sc[r] + 1.0f, v[e + r], sh[r]));
                     }
                 }
                 u32x4 w0, w1;
@@ -455,7 +456,7 @@ static_assert(S_ZERO % 256 == 0, "the zero region mirrors the bank position of t
 // WD = image width (16 or 32: a template parameter, so that which fragments of a wave end at a row end is known to the compiler):
 // a fragment is 16 pixels of one image row; at WD = 32 the even fragments of a wave start a row and the odd ones end it, at
 // WD = 16 every fragment does both.
-template <int EPI, int WD>
+template <int EPI, int WD, int ACT = BSI_ACT_SILU>
 __global__ __launch_bounds__(512) void conv_slab_kernel(const ConvParams p) {
     constexpr int TM = 8, NW = 8;
     constexpr unsigned XL = WD == 32 ? 0x55u : 0xffu, XR = WD == 32 ? 0xaau : 0xffu;  // fragments with a pixel in column 0 / WD-1
@@ -590,7 +591,7 @@ __global__ __launch_bounds__(512) void conv_slab_kernel(const ConvParams p) {
         if constexpr (BF16_OUT) {
             if (nb >= p.N) return;
             // FiLM + SiLU per (image, channel); the wave's 128 rows lie in ONE image (launcher: H*W % 128 == 0)
-            if constexpr (EPI == CEPI_FILM_SILU_BF16) film_silu_inplace(p, acc, mw0, nb, HW);
+            if constexpr (EPI == CEPI_FILM_SILU_BF16) film_act_inplace<ACT>(p, acc, mw0, nb, HW);
 #pragma unroll
             for (int j = 0; j < TM; ++j) {
                 f32x4 v[4] = {acc[0][j], acc[1][j], acc[2][j], acc[3][j]};
@@ -780,7 +781,7 @@ constexpr int S2_WSLOTS = 6, S2_WD = 5;
 constexpr int S2_ZERO = S2_WRING + S2_WSLOTS * S_WSTAGE, S2_LDS = S2_ZERO + 256;
 static_assert(S2_ZERO % 256 == 0 && S2_LDS <= 160 * 1024, "LDS image of the two-source slab kernel");
 
-template <int EPI, int WD>
+template <int EPI, int WD, int ACT = BSI_ACT_SILU>
 __global__ __launch_bounds__(512) void conv_slab2_kernel(const ConvParams p) {
     constexpr int TM = 8, NW = 8;
     constexpr unsigned XL = WD == 32 ? 0x55u : 0xffu, XR = WD == 32 ? 0xaau : 0xffu;
@@ -915,7 +916,7 @@ __global__ __launch_bounds__(512) void conv_slab2_kernel(const ConvParams p) {
         if (nb0 >= p.N || (BSI_ABL(p.abl, 4))) return;
         if constexpr (BF16_OUT) {
             if (nb >= p.N) return;
-            if constexpr (EPI == CEPI_FILM_SILU_BF16) film_silu_inplace(p, acc, mw0, nb, HW);
+            if constexpr (EPI == CEPI_FILM_SILU_BF16) film_act_inplace<ACT>(p, acc, mw0, nb, HW);
 #pragma unroll
             for (int j = 0; j < TM; ++j) {
                 f32x4 v[4] = {acc[0][j], acc[1][j], acc[2][j], acc[3][j]};
@@ -1086,14 +1087,14 @@ int conv_cus() {
     return cus;
 }
 
-template <int EPI>
+template <int EPI, int ACT>
 int launch_conv_slab(const ConvParams& p, int grid, hipStream_t s) {
     if (p.Wd == 32) {
-        auto kern = conv_slab_kernel<EPI, 32>;
+        auto kern = conv_slab_kernel<EPI, 32, ACT>;
         set_max_lds(reinterpret_cast<const void*>(kern), (int)S_LDS);
         hipLaunchKernelGGL(kern, dim3(grid), dim3(512), S_LDS, s, p);
     } else {
-        auto kern = conv_slab_kernel<EPI, 16>;
+        auto kern = conv_slab_kernel<EPI, 16, ACT>;
         set_max_lds(reinterpret_cast<const void*>(kern), (int)S_LDS);
         hipLaunchKernelGGL(kern, dim3(grid), dim3(512), S_LDS, s, p);
     }
@@ -1101,7 +1102,7 @@ int launch_conv_slab(const ConvParams& p, int grid, hipStream_t s) {
     return BSI_OK;
 }
 
-template <int EPI>
+template <int EPI, int ACT = BSI_ACT_SILU>
 int launch_conv(ConvParams p, hipStream_t s) {
     p.tiles_m = (p.M + C_BM - 1) / C_BM;
     p.abl = g_conv_abl;
@@ -1128,11 +1129,11 @@ int launch_conv(ConvParams p, hipStream_t s) {
         // the A/B partner of tools/unet_bench.py)
         if (p.taps == 9 && p.Cin2 == 2 * p.Cin && p.Cin2 > 0 && (p.Wd == 16 || p.Wd == 32) && p.N % C_BN == 0 && !(g_conv_abl & (256 | 8192))) {
             if (p.Wd == 32) {
-                auto kern = conv_slab2_kernel<EPI, 32>;
+                auto kern = conv_slab2_kernel<EPI, 32, ACT>;
                 set_max_lds(reinterpret_cast<const void*>(kern), (int)S2_LDS);
                 hipLaunchKernelGGL(kern, dim3(grid), dim3(512), S2_LDS, s, p);
             } else {
-                auto kern = conv_slab2_kernel<EPI, 16>;
+                auto kern = conv_slab2_kernel<EPI, 16, ACT>;
                 set_max_lds(reinterpret_cast<const void*>(kern), (int)S2_LDS);
                 hipLaunchKernelGGL(kern, dim3(grid), dim3(512), S2_LDS, s, p);
             }
@@ -1146,10 +1147,10 @@ int launch_conv(ConvParams p, hipStream_t s) {
                           : F32 ? !(g_conv_abl & 4096)
                           : EPI == CEPI_FILM_SILU_BF16 ? !(g_conv_abl & 2048)
                                                        : true;
-        if (can && want) return launch_conv_slab<EPI>(p, grid, s);
+        if (can && want) return launch_conv_slab<EPI, ACT>(p, grid, s);
     }
     const size_t lds = (size_t)C_R * C_SLOT;
-    auto kern = conv_ring_kernel<EPI>;
+    auto kern = conv_ring_kernel<EPI, ACT>;
     set_max_lds(reinterpret_cast<const void*>(kern), (int)lds);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, s, p);
     BSI_CHECK_LAUNCH("bsi_conv_nhwc_bf16");
@@ -1204,8 +1205,14 @@ extern "C" int bsi_conv_nhwc_bf16(const bsi_conv_args* a, bsi_stream_t stream) {
         case BSI_CONV_BIAS_BF16: return launch_conv<CEPI_BIAS_BF16>(p, s);
         case BSI_CONV_FILM_SILU_BF16:
             BSI_CHECK_ARG(a->film, "bsi_conv_nhwc_bf16: FILM epilogue needs the (scale, shift) table");
-            if ((a->H * a->W) % 128 == 0) return launch_conv<CEPI_FILM_SILU_BF16>(p, s);
-            return launch_conv<CEPI_FILM_ROWS_SILU_BF16>(p, s);
+            BSI_CHECK_ARG(a->act >= BSI_ACT_NONE && a->act <= BSI_ACT_TANH, "bsi_conv_nhwc_bf16: unknown activation code %d", a->act);
+            // act 0 reads as SiLU (callers that zero-initialise the arguments); the FiLM epilogue always has an activation
+            return bsi_with_act(a->act == BSI_ACT_NONE ? BSI_ACT_SILU : a->act, "bsi_conv_nhwc_bf16", [&](auto ac) {
+                constexpr int ACT = decltype(ac)::value;
+                if constexpr (ACT == BSI_ACT_NONE) return BSI_EINVAL;  // unreachable (mapped to SiLU above); no instantiation
+                else if ((a->H * a->W) % 128 == 0) return launch_conv<CEPI_FILM_SILU_BF16, ACT>(p, s);
+                else return launch_conv<CEPI_FILM_ROWS_SILU_BF16, ACT>(p, s);
+            });
         case BSI_CONV_BIAS_RESID_F32:
             if (a->gn_partial) {
                 // a wave's 128-row x 64-column block must be whole and lie in one image

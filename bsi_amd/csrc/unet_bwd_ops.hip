@@ -1,5 +1,5 @@
 // Memory-bound kernels of the VDM-UNet TRAINING path (autograd of bsi/nn/residual_block.py:21-24,40-48,61-64 and
-// bsi/models/vdm_unet.py:72,100 of the reference): FiLM + SiLU + Dropout forward/backward, GroupNorm(+SiLU) backward,
+// bsi/models/vdm_unet.py:72,100 of the reference): FiLM + ActFn + Dropout forward/backward, GroupNorm(+ActFn) backward,
 // backward of the fp32 1x1 decode convolution.
 #include <math.h>
 
@@ -13,9 +13,12 @@ int bsi_reduce_slabs2_launch(const float* slabsA, size_t strideA, size_t nA, flo
 
 namespace {
 
-__device__ __forceinline__ float silu_grad_f(float z) {
-    const float s = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * z));
-    return s * (1.0f + z * (1.0f - s));
+// dz of the GroupNorm backward: da * act'(z) at the recomputed pre-activation z = n*gamma + beta.  ACT_FLAG: the run-time flag `silu`
+// (0: none, 1: SiLU) as these kernels always had it; another code: that activation.
+template <int ACT>
+__device__ __forceinline__ float gn_dz(float g, float nrm, float ga, float be, int silu) {
+    if constexpr (ACT == ACT_FLAG) return silu ? g * silu_grad_f(__fmaf_rn(nrm, ga, be)) : g;
+    else return g * act_grad_f<ACT>(__fmaf_rn(nrm, ga, be));
 }
 
 __device__ __forceinline__ void unpack8(const u32x4 w, float* v) {
@@ -26,8 +29,20 @@ __device__ __forceinline__ void unpack8(const u32x4 w, float* v) {
     }
 }
 
-// y = Dropout(SiLU(h1 * (scale + 1) + shift))  (FeatureModulation: addcmul(shift, scale + 1, y), residual_block.py:21-24,
-// then ActFn and nn.Dropout, :44-46).  h1, y bf16 [M, N]; film row of pixel m = (m / HW) % film_rows.
+// out = bf16(act(pre)) and bf16(ds * act'(pre)) elementwise (the pos_map activations of the training engine, vdm_unet.py:65-69)
+template <int ACT>
+__global__ void act_bf16_kernel(const float* __restrict__ pre, size_t n, __bf16* __restrict__ out) {
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) out[i] = (__bf16)act_f<ACT>(pre[i]);
+}
+template <int ACT>
+__global__ void act_bwd_bf16_kernel(const float* __restrict__ ds, const float* __restrict__ pre, size_t n, __bf16* __restrict__ out) {
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
+        out[i] = (__bf16)(ds[i] * act_grad_f<ACT>(pre[i]));
+}
+
+// y = Dropout(ActFn(h1 * (scale + 1) + shift))  (FeatureModulation: addcmul(shift, scale + 1, y), residual_block.py:21-24,
+// then ActFn and nn.Dropout, :44-46).  h1, y bf16 [M, N]; film row of pixel m = (m / HW) % film_rows.  ACT: BSI_ACT_*.
+template <int ACT>
 __global__ void film_silu_drop_kernel(const __bf16* __restrict__ h1, unsigned M, int N, int HW, const float* __restrict__ film,
                                       int film_rows, int film_stride, DropCfg dc, __bf16* __restrict__ y) {
     const unsigned n8 = N / 8;
@@ -45,7 +60,7 @@ __global__ void film_silu_drop_kernel(const __bf16* __restrict__ h1, unsigned M,
         *reinterpret_cast<f32x4*>(sh + 4) = *reinterpret_cast<const f32x4*>(fr + N + c + 4);
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-            float u = silu_f(__fmaf_rn(sc[e] + 1.0f, v[e], sh[e]));
+            float u = act_f<ACT>(__fmaf_rn(sc[e] + 1.0f, v[e], sh[e]));
             if (dc.thr) u = drop_keep_rc(dc, rh, c + e) ? u * dc.scale : 0.0f;  // element (row = pixel, column = channel)
             v[e] = u;
         }
@@ -56,10 +71,11 @@ __global__ void film_silu_drop_kernel(const __bf16* __restrict__ h1, unsigned M,
     }
 }
 
-// Backward of the above: dU = dy * mask/(1-p) * silu'(u), u = h1*(scale+1)+shift;
+// Backward of the above: dU = dy * mask/(1-p) * act'(u), u = h1*(scale+1)+shift;
 //   dh1 = dU * (scale + 1)  (bf16),  dscale[b, n] += sum_p dU * h1,  dshift[b, n] += sum_p dU.
 // One workgroup (256 threads) per slab of FB_ROWS pixels of one image; thread = (8-channel chunk, pixel sub-row).
 constexpr int FB_ROWS = 64;
+template <int ACT>
 __global__ __launch_bounds__(256) void film_silu_bwd_kernel(const __bf16* __restrict__ dy, const __bf16* __restrict__ h1, int N,
                                                             int HW, const float* __restrict__ film, int film_rows,
                                                             int film_stride, DropCfg dc, __bf16* __restrict__ dh1,
@@ -85,7 +101,7 @@ __global__ __launch_bounds__(256) void film_silu_bwd_kernel(const __bf16* __rest
         unpack8(*reinterpret_cast<const u32x4*>(h1 + m * N + c), h);
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-            float du = g[e] * silu_grad_f(__fmaf_rn(sc1[e], h[e], sh[e]));
+            float du = g[e] * act_grad_f<ACT>(__fmaf_rn(sc1[e], h[e], sh[e]));
             if (dc.thr) du = drop_keep_rc(dc, rh, c + e) ? du * dc.scale : 0.0f;
             gs[e] = __fmaf_rn(du, h[e], gs[e]);
             gh[e] += du;
@@ -109,11 +125,12 @@ __global__ __launch_bounds__(256) void film_silu_bwd_kernel(const __bf16* __rest
     }
 }
 
-// Backward of GroupNorm(32, affine)(+ SiLU) over cat(x1, x2) of one image (see groupnorm_kernel):
-//   z = n*gamma + beta, n = (x - mean)*rstd;  dz = da * silu'(z) (or da);  dgamma += sum dz*n, dbeta += sum dz,
+// Backward of GroupNorm(32, affine)(+ activation) over cat(x1, x2) of one image (see groupnorm_kernel):
+//   z = n*gamma + beta, n = (x - mean)*rstd;  dz = da * act'(z) (gn_dz);  dgamma += sum dz*n, dbeta += sum dz,
 //   dn = dz*gamma;  dx = rstd * (dn - mean_g(dn) - n * mean_g(dn * n));   out = dx (+ add) (+ add_b on the x1 part).
 // Grid (image, 32-channel slice) like the forward kernel; three passes (statistics; group sums and affine gradients; write).
 constexpr int GN_CS = 32, GN_TPB = 256;
+template <int ACT>
 __global__ __launch_bounds__(GN_TPB) void groupnorm_bwd_kernel(const __bf16* __restrict__ da, const float* __restrict__ x1, int C1,
                                                              const float* __restrict__ x2, int C2, int HW,
                                                              const float* __restrict__ gamma, const float* __restrict__ beta,
@@ -179,7 +196,7 @@ __global__ __launch_bounds__(GN_TPB) void groupnorm_bwd_kernel(const __bf16* __r
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             nrm[k] = (v[k] - mean[k]) * rstd[k];
-            dz[k] = silu ? g[k] * silu_grad_f(__fmaf_rn(nrm[k], ga[k], be[k])) : g[k];
+            dz[k] = gn_dz<ACT>(g[k], nrm[k], ga[k], be[k], silu);
         }
     };
     // ---- pass 1: group sums of dn and dn*n, per-channel dgamma / dbeta
@@ -278,7 +295,7 @@ __global__ __launch_bounds__(GN_TPB) void groupnorm_bwd_kernel(const __bf16* __r
 // Deterministic like the streaming kernel (the partial sums are cut by 64 instead of 32 row classes: other last bits).
 constexpr int GNR_TPB = 512;  // 64 pixel rows in parallel: 16 resident rows per thread at 32 x 32 pixels (with 256 threads and 32 rows hipcc
                                // schedules itself to 490 registers, or spills at 256)
-template <int ROWS, int CT, int CSRC>  // channels of cat(x1, x2) (= row pitch of dA / add), channels of x1 and of x2 (= their row pitch)
+template <int ROWS, int CT, int CSRC, int ACT>  // channels of cat(x1, x2) (= row pitch of dA / add), channels of x1 and of x2 (= their row pitch)
 __global__ __launch_bounds__(GNR_TPB) void groupnorm_bwd_res_kernel(const __bf16* __restrict__ da, const float* __restrict__ x1, int C1,
                                                              const float* __restrict__ x2, int C2, int HW,
                                                              const float* __restrict__ gamma, const float* __restrict__ beta,
@@ -357,7 +374,7 @@ __global__ __launch_bounds__(GNR_TPB) void groupnorm_bwd_res_kernel(const __bf16
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             nrm[k] = (v[k] - mean[k]) * rstd[k];
-            dz[k] = silu ? g[k] * silu_grad_f(__fmaf_rn(nrm[k], ga[k], be[k])) : g[k];
+            dz[k] = gn_dz<ACT>(g[k], nrm[k], ga[k], be[k], silu);
         }
     };
     // ---- pass 1: group sums of dn and dn*n, per-channel dgamma / dbeta
@@ -506,48 +523,89 @@ __global__ __launch_bounds__(256) void unet_decode_bwd_kernel(const float* __res
 
 #define S_(stream) reinterpret_cast<hipStream_t>(stream)
 
-int bsi_film_silu_drop(const void* h1, int M, int N, int HW, const float* film, int film_rows, int film_stride, DropCfg dc,
-                       void* y, bsi_stream_t stream) {
+int bsi_film_act_drop(const void* h1, int M, int N, int HW, const float* film, int film_rows, int film_stride, int act, DropCfg dc,
+                      void* y, bsi_stream_t stream) {
     BSI_CHECK_ARG(h1 && film && y && M > 0 && N > 0 && N % 8 == 0 && HW > 0 && film_rows > 0 && film_stride % 4 == 0 &&
                       (size_t)M * N < (1ull << 32),
                   "bsi_film_silu: bad args");
     size_t g = ((size_t)M * (N / 8) + 255) / 256;
     if (g > 16384) g = 16384;
-    hipLaunchKernelGGL(film_silu_drop_kernel, dim3((int)g), dim3(256), 0, S_(stream), reinterpret_cast<const __bf16*>(h1), (unsigned)M,
-                       N, HW, film, film_rows, film_stride, dc, reinterpret_cast<__bf16*>(y));
-    BSI_CHECK_LAUNCH("bsi_film_silu");
-    return BSI_OK;
+    return bsi_with_act(act, "bsi_film_act", [&](auto a) {
+        hipLaunchKernelGGL(film_silu_drop_kernel<decltype(a)::value>, dim3((int)g), dim3(256), 0, S_(stream), reinterpret_cast<const __bf16*>(h1),
+                           (unsigned)M, N, HW, film, film_rows, film_stride, dc, reinterpret_cast<__bf16*>(y));
+        BSI_CHECK_LAUNCH("bsi_film_silu");
+        return BSI_OK;
+    });
 }
 
-int bsi_film_silu_bwd_drop(const void* dy, const void* h1, int M, int N, int HW, const float* film, int film_rows,
-                           int film_stride, DropCfg dc, void* dh1, float* dfilm, int dfilm_stride, bsi_stream_t stream,
+int bsi_film_act_bwd_drop(const void* dy, const void* h1, int M, int N, int HW, const float* film, int film_rows,
+                          int film_stride, int act, DropCfg dc, void* dh1, float* dfilm, int dfilm_stride, bsi_stream_t stream,
                            size_t part_stride) {
     BSI_CHECK_ARG(dy && h1 && film && dh1 && dfilm && M > 0, "bsi_film_silu_bwd: bad args");
     BSI_CHECK_ARG((N == 64 || N == 128) && HW % FB_ROWS == 0 && M % HW == 0 && film_rows > 0,
                   "bsi_film_silu_bwd: N=%d (64 or 128), HW=%d (multiple of %d)", N, HW, FB_ROWS);
-    hipLaunchKernelGGL(film_silu_bwd_kernel, dim3(M / FB_ROWS), dim3(256), 0, S_(stream), reinterpret_cast<const __bf16*>(dy),
-                       reinterpret_cast<const __bf16*>(h1), N, HW, film, film_rows, film_stride, dc,
-                       reinterpret_cast<__bf16*>(dh1), dfilm, dfilm_stride, part_stride);
-    BSI_CHECK_LAUNCH("bsi_film_silu_bwd");
-    return BSI_OK;
+    return bsi_with_act(act, "bsi_film_act_bwd", [&](auto a) {
+        hipLaunchKernelGGL(film_silu_bwd_kernel<decltype(a)::value>, dim3(M / FB_ROWS), dim3(256), 0, S_(stream),
+                           reinterpret_cast<const __bf16*>(dy), reinterpret_cast<const __bf16*>(h1), N, HW, film, film_rows, film_stride, dc,
+                           reinterpret_cast<__bf16*>(dh1), dfilm, dfilm_stride, part_stride);
+        BSI_CHECK_LAUNCH("bsi_film_silu_bwd");
+        return BSI_OK;
+    });
+}
+
+extern "C" int bsi_film_act(const void* h1, int M, int N, int HW, const float* film, int film_rows, int film_stride, int act,
+                            float dropout_p, unsigned long long seed, unsigned site, void* y, bsi_stream_t stream) {
+    BSI_CHECK_ARG(dropout_p >= 0.f && dropout_p < 1.f, "bsi_film_act: dropout probability %g outside [0, 1)", (double)dropout_p);
+    return bsi_film_act_drop(h1, M, N, HW, film, film_rows, film_stride, act, make_drop(dropout_p, seed, site), y, stream);
+}
+
+extern "C" int bsi_film_act_bwd(const void* dy, const void* h1, int M, int N, int HW, const float* film, int film_rows,
+                                int film_stride, int act, float dropout_p, unsigned long long seed, unsigned site, void* dh1,
+                                float* dfilm, int dfilm_stride, bsi_stream_t stream) {
+    BSI_CHECK_ARG(dropout_p >= 0.f && dropout_p < 1.f, "bsi_film_act_bwd: dropout probability %g outside [0, 1)", (double)dropout_p);
+    return bsi_film_act_bwd_drop(dy, h1, M, N, HW, film, film_rows, film_stride, act, make_drop(dropout_p, seed, site), dh1, dfilm,
+                                 dfilm_stride, stream, 0);
+}
+
+extern "C" int bsi_act_bf16(const float* pre, size_t n, int act, void* out, bsi_stream_t stream) {
+    if (act == BSI_ACT_SILU) return bsi_silu_bf16(pre, n, out, stream);  // the DiT's kernel: SiLU models keep their bits
+    BSI_CHECK_ARG(pre && out && n > 0, "bsi_act_bf16: bad args");
+    size_t g = (n + 255) / 256;
+    if (g > 4096) g = 4096;
+    return bsi_with_act(act, "bsi_act_bf16", [&](auto a) {
+        hipLaunchKernelGGL(act_bf16_kernel<decltype(a)::value>, dim3((int)g), dim3(256), 0, S_(stream), pre, n, reinterpret_cast<__bf16*>(out));
+        BSI_CHECK_LAUNCH("bsi_act_bf16");
+        return BSI_OK;
+    });
+}
+
+extern "C" int bsi_act_bwd_bf16(const float* ds, const float* pre, size_t n, int act, void* out, bsi_stream_t stream) {
+    BSI_CHECK_ARG(ds && pre && out && n > 0, "bsi_act_bwd_bf16: bad args");
+    if (act == BSI_ACT_SILU) return bsi_silu_bwd_bf16(ds, pre, n, out, stream);
+    size_t g = (n + 255) / 256;
+    if (g > 4096) g = 4096;
+    return bsi_with_act(act, "bsi_act_bwd_bf16", [&](auto a) {
+        hipLaunchKernelGGL(act_bwd_bf16_kernel<decltype(a)::value>, dim3((int)g), dim3(256), 0, S_(stream), ds, pre, n,
+                           reinterpret_cast<__bf16*>(out));
+        BSI_CHECK_LAUNCH("bsi_act_bwd_bf16");
+        return BSI_OK;
+    });
 }
 
 extern "C" int bsi_film_silu(const void* h1, int M, int N, int HW, const float* film, int film_rows, int film_stride,
                              float dropout_p, unsigned long long seed, unsigned site, void* y, bsi_stream_t stream) {
-    BSI_CHECK_ARG(dropout_p >= 0.f && dropout_p < 1.f, "bsi_film_silu: dropout probability %g outside [0, 1)", (double)dropout_p);
-    return bsi_film_silu_drop(h1, M, N, HW, film, film_rows, film_stride, make_drop(dropout_p, seed, site), y, stream);
+    return bsi_film_act(h1, M, N, HW, film, film_rows, film_stride, BSI_ACT_SILU, dropout_p, seed, site, y, stream);
 }
 
 extern "C" int bsi_film_silu_bwd(const void* dy, const void* h1, int M, int N, int HW, const float* film, int film_rows,
                                  int film_stride, float dropout_p, unsigned long long seed, unsigned site, void* dh1,
                                  float* dfilm, int dfilm_stride, bsi_stream_t stream) {
-    BSI_CHECK_ARG(dropout_p >= 0.f && dropout_p < 1.f, "bsi_film_silu_bwd: dropout probability %g outside [0, 1)", (double)dropout_p);
-    return bsi_film_silu_bwd_drop(dy, h1, M, N, HW, film, film_rows, film_stride, make_drop(dropout_p, seed, site), dh1, dfilm,
-                                  dfilm_stride, stream, 0);
+    return bsi_film_act_bwd(dy, h1, M, N, HW, film, film_rows, film_stride, BSI_ACT_SILU, dropout_p, seed, site, dh1, dfilm, dfilm_stride,
+                            stream);
 }
 
 static int groupnorm_bwd_impl(const void* da, const float* x1, int C1, const float* x2, int C2, int B, int HW, const float* gamma,
-                              const float* beta, float eps, int silu, const float* add, const float* add_b, float* out1, float* out2,
+                              const float* beta, float eps, int act, const float* add, const float* add_b, float* out1, float* out2,
                               float* dgamma, float* dbeta, void* out1_bf16, const float* stats, bsi_stream_t stream,
                               float* partials = nullptr) {
     BSI_CHECK_ARG(da && x1 && gamma && beta && out1 && dgamma && dbeta && B > 0 && HW > 0, "bsi_groupnorm_bwd_nhwc: bad args");
@@ -557,18 +615,25 @@ static int groupnorm_bwd_impl(const void* da, const float* x1, int C1, const flo
     // per launch at 128 images (tools/experiments/gn_bwd_ab.sh): 128 channels 76.6 against 80.6 us streaming, cat(x, skip) with 256 channels 125.1
     // against 150.8.  BSI_GN_BWD_STREAM=1: the streaming kernel everywhere (the A/B partner; other last bits).
     static const bool streaming = getenv("BSI_GN_BWD_STREAM") != nullptr;
-    if (HW == 1024 && C1 == 128 && C2 == 0 && !streaming)
-        hipLaunchKernelGGL((groupnorm_bwd_res_kernel<16, 128, 128>), dim3(B, C / GN_CS), dim3(GNR_TPB), 0, S_(stream), reinterpret_cast<const __bf16*>(da),
-                           x1, C1, x2, C2, HW, gamma, beta, eps, silu, add, add_b, out1, out2, dgamma, dbeta, reinterpret_cast<__bf16*>(out1_bf16),
-                           stats, partials);
-    else if (HW == 1024 && C1 == 128 && C2 == 128 && !streaming)
-        hipLaunchKernelGGL((groupnorm_bwd_res_kernel<16, 256, 128>), dim3(B, C / GN_CS), dim3(GNR_TPB), 0, S_(stream), reinterpret_cast<const __bf16*>(da),
-                           x1, C1, x2, C2, HW, gamma, beta, eps, silu, add, add_b, out1, out2, dgamma, dbeta, reinterpret_cast<__bf16*>(out1_bf16),
-                           stats, partials);
-    else
-        hipLaunchKernelGGL(groupnorm_bwd_kernel, dim3(B, C / GN_CS), dim3(GN_TPB), 0, S_(stream), reinterpret_cast<const __bf16*>(da), x1, C1, x2, C2,
-                           HW, gamma, beta, eps, silu, add, add_b, out1, out2, dgamma, dbeta, reinterpret_cast<__bf16*>(out1_bf16), stats, partials);
-    BSI_CHECK_LAUNCH("bsi_groupnorm_bwd_nhwc");
+    const int rc = bsi_with_act_flag(act, "bsi_groupnorm_bwd_nhwc", [&](auto a) {
+        constexpr int ACT = decltype(a)::value;
+        const int silu = act;  // the flag of the ACT_FLAG instantiation
+        if (HW == 1024 && C1 == 128 && C2 == 0 && !streaming)
+            hipLaunchKernelGGL((groupnorm_bwd_res_kernel<16, 128, 128, ACT>), dim3(B, C / GN_CS), dim3(GNR_TPB), 0, S_(stream),
+                               reinterpret_cast<const __bf16*>(da), x1, C1, x2, C2, HW, gamma, beta, eps, silu, add, add_b, out1, out2, dgamma, dbeta,
+                               reinterpret_cast<__bf16*>(out1_bf16), stats, partials);
+        else if (HW == 1024 && C1 == 128 && C2 == 128 && !streaming)
+            hipLaunchKernelGGL((groupnorm_bwd_res_kernel<16, 256, 128, ACT>), dim3(B, C / GN_CS), dim3(GNR_TPB), 0, S_(stream),
+                               reinterpret_cast<const __bf16*>(da), x1, C1, x2, C2, HW, gamma, beta, eps, silu, add, add_b, out1, out2, dgamma, dbeta,
+                               reinterpret_cast<__bf16*>(out1_bf16), stats, partials);
+        else
+            hipLaunchKernelGGL(groupnorm_bwd_kernel<ACT>, dim3(B, C / GN_CS), dim3(GN_TPB), 0, S_(stream), reinterpret_cast<const __bf16*>(da), x1,
+                               C1, x2, C2, HW, gamma, beta, eps, silu, add, add_b, out1, out2, dgamma, dbeta, reinterpret_cast<__bf16*>(out1_bf16),
+                               stats, partials);
+        BSI_CHECK_LAUNCH("bsi_groupnorm_bwd_nhwc");
+        return BSI_OK;
+    });
+    if (rc != BSI_OK) return rc;
     if (partials) {  // dgamma / dbeta are WRITTEN: per-image rows summed in image order
         return bsi_reduce_slabs2_launch(partials, (size_t)2 * C, (size_t)C, dgamma, partials + C, (size_t)2 * C, (size_t)C, dbeta, B, 0, S_(stream));
     }
@@ -577,26 +642,26 @@ static int groupnorm_bwd_impl(const void* da, const float* x1, int C1, const flo
 
 // engine-internal (unet_ops.h): the reproducible form of bsi_groupnorm_bwd_cast_nhwc -- `partials`: B * 2 * (C1 + C2) floats of scratch
 int bsi_groupnorm_bwd_cast_det(const void* da, const float* x1, int C1, const float* x2, int C2, int B, int HW, const float* gamma,
-                               const float* beta, float eps, int silu, const float* add, const float* add_b, float* out1, float* out2,
+                               const float* beta, float eps, int act, const float* add, const float* add_b, float* out1, float* out2,
                                float* dgamma, float* dbeta, void* out1_bf16, const float* stats, float* partials, bsi_stream_t stream) {
     BSI_CHECK_ARG(out1_bf16 && partials, "bsi_groupnorm_bwd_cast_det: bf16 output or scratch missing");
-    return groupnorm_bwd_impl(da, x1, C1, x2, C2, B, HW, gamma, beta, eps, silu, add, add_b, out1, out2, dgamma, dbeta, out1_bf16, stats, stream,
+    return groupnorm_bwd_impl(da, x1, C1, x2, C2, B, HW, gamma, beta, eps, act, add, add_b, out1, out2, dgamma, dbeta, out1_bf16, stats, stream,
                               partials);
 }
 
 extern "C" int bsi_groupnorm_bwd_nhwc(const void* da, const float* x1, int C1, const float* x2, int C2, int B, int HW,
-                                      const float* gamma, const float* beta, float eps, int silu, const float* add,
+                                      const float* gamma, const float* beta, float eps, int act, const float* add,
                                       const float* add_b, float* out1, float* out2, float* dgamma, float* dbeta,
                                       bsi_stream_t stream) {
-    return groupnorm_bwd_impl(da, x1, C1, x2, C2, B, HW, gamma, beta, eps, silu, add, add_b, out1, out2, dgamma, dbeta, nullptr, nullptr, stream);
+    return groupnorm_bwd_impl(da, x1, C1, x2, C2, B, HW, gamma, beta, eps, act, add, add_b, out1, out2, dgamma, dbeta, nullptr, nullptr, stream);
 }
 
 extern "C" int bsi_groupnorm_bwd_cast_nhwc(const void* da, const float* x1, int C1, const float* x2, int C2, int B, int HW,
-                                           const float* gamma, const float* beta, float eps, int silu, const float* add,
+                                           const float* gamma, const float* beta, float eps, int act, const float* add,
                                            const float* add_b, float* out1, float* out2, float* dgamma, float* dbeta,
                                            void* out1_bf16, const float* stats, bsi_stream_t stream) {
     BSI_CHECK_ARG(out1_bf16, "bsi_groupnorm_bwd_cast_nhwc: bf16 output missing");
-    return groupnorm_bwd_impl(da, x1, C1, x2, C2, B, HW, gamma, beta, eps, silu, add, add_b, out1, out2, dgamma, dbeta, out1_bf16, stats, stream);
+    return groupnorm_bwd_impl(da, x1, C1, x2, C2, B, HW, gamma, beta, eps, act, add, add_b, out1, out2, dgamma, dbeta, out1_bf16, stats, stream);
 }
 
 extern "C" int bsi_unet_decode_bwd(const float* g_xhat, const float* c_out, int coef_stride, const float* h, int B, int HW, int C,

@@ -99,9 +99,10 @@ inline UWs carve(const bsi_unet_config* c, int B, void* base) {
 
 int conv(const void* x, const void* x2, const void* w, const float* bias, const void* zeros, void* out, const float* film,
          int film_rows, int film_stride, const float* resid, int B, int H, int W, int Cin, int Cin2, int Cout, int taps, int epi,
-         bsi_stream_t s, float* gn_part = nullptr) {
+         bsi_stream_t s, float* gn_part = nullptr, int act = BSI_ACT_SILU) {
     bsi_conv_args a{};
     a.gn_partial = gn_part;
+    a.act = act;
     a.x = x; a.x2 = x2; a.w = w; a.bias = bias; a.zeros = zeros; a.out = out; a.film = film; a.film_rows = film_rows;
     a.film_stride = film_stride; a.resid = resid; a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cin2 = Cin2; a.Cout = Cout;
     a.taps = taps; a.ldo = Cout; a.epilogue = epi;
@@ -109,6 +110,12 @@ int conv(const void* x, const void* x2, const void* w, const float* bias, const 
 }
 
 }  // namespace
+
+// The model's ActFn (bsi_unet_weights.actfn, 0 = SiLU); -1 for an unknown code.
+int unet_actfn(const bsi_unet_weights* w) {
+    const int a = w->actfn == BSI_ACT_NONE ? BSI_ACT_SILU : w->actfn;
+    return a >= BSI_ACT_SILU && a <= BSI_ACT_TANH ? a : -1;
+}
 
 extern "C" size_t bsi_unet_workspace_bytes(const bsi_unet_config* cfg, int B) {
     if (!cfg || B <= 0) return 0;
@@ -130,6 +137,9 @@ extern "C" int bsi_unet_film(const bsi_unet_config* cfg, const bsi_unet_weights*
     BSI_CHECK_ARG(cfg->emb_size <= 64 && cfg->emb_size % 2 == 0 && cfg->c_dim % 64 == 0, "bsi_unet_film: emb_size=%d c_dim=%d unsupported",
                   cfg->emb_size, cfg->c_dim);
     const UDims d = udims(cfg, 1);
+    const int act = unet_actfn(w);
+    BSI_CHECK_ARG(act > 0, "bsi_unet_film: unknown activation code %d", w->actfn);
+    BSI_CHECK_ARG(act == BSI_ACT_SILU || cfg->c_dim <= d.nblocks * 2 * cfg->dim, "bsi_unet_film: c_dim=%d exceeds a FiLM row", cfg->c_dim);
     char* p = reinterpret_cast<char*>(scratch);
     const size_t cb = au((size_t)rows * (cfg->c_dim > 64 ? cfg->c_dim : 64) * 2);
     char* emb = p;            // bf16 [rows, 64] (zero padded)
@@ -138,14 +148,19 @@ extern "C" int bsi_unet_film(const bsi_unet_config* cfg, const bsi_unet_weights*
     float* embf = reinterpret_cast<float*>(p + 3 * cb);
     TRY(bsi_nyquist_embed(t, rows, w->pe_scale, w->pe_bias, cfg->emb_size, embf, nullptr, stream));
     TRY(bsi_cast_rows_bf16(embf, cfg->emb_size, rows, cfg->emb_size, emb, 64, stream));
+    // pos_map.1-4: Linear -> ActFn -> Linear -> ActFn.  SiLU is the GEMM's fused epilogue; another activation takes the fp32
+    // pre-activation (parked in `film`, which the last GEMM overwrites) through bsi_act_bf16, as the training engine does.
+    const bool fused = act == BSI_ACT_SILU;
     bsi_gemm_args g{};
-    g.A = emb; g.W = w->pm1_w; g.bias = w->pm1_b; g.out = c1; g.M = rows; g.N = cfg->c_dim; g.K = 64; g.lda = 64; g.ldw = 64;
-    g.ldo = cfg->c_dim; g.epilogue = BSI_EPI_BIAS_SILU_BF16;
+    g.A = emb; g.W = w->pm1_w; g.bias = w->pm1_b; g.out = fused ? (void*)c1 : (void*)film; g.M = rows; g.N = cfg->c_dim; g.K = 64; g.lda = 64;
+    g.ldw = 64; g.ldo = cfg->c_dim; g.epilogue = fused ? BSI_EPI_BIAS_SILU_BF16 : BSI_EPI_BIAS_F32;
     TRY(bsi_gemm_bf16(&g, stream));
+    if (!fused) TRY(bsi_act_bf16(film, (size_t)rows * cfg->c_dim, act, c1, stream));
     bsi_gemm_args g2{};
-    g2.A = c1; g2.W = w->pm3_w; g2.bias = w->pm3_b; g2.out = c2; g2.M = rows; g2.N = cfg->c_dim; g2.K = cfg->c_dim;
-    g2.lda = cfg->c_dim; g2.ldw = cfg->c_dim; g2.ldo = cfg->c_dim; g2.epilogue = BSI_EPI_BIAS_SILU_BF16;
+    g2.A = c1; g2.W = w->pm3_w; g2.bias = w->pm3_b; g2.out = fused ? (void*)c2 : (void*)film; g2.M = rows; g2.N = cfg->c_dim; g2.K = cfg->c_dim;
+    g2.lda = cfg->c_dim; g2.ldw = cfg->c_dim; g2.ldo = cfg->c_dim; g2.epilogue = fused ? BSI_EPI_BIAS_SILU_BF16 : BSI_EPI_BIAS_F32;
     TRY(bsi_gemm_bf16(&g2, stream));
+    if (!fused) TRY(bsi_act_bf16(film, (size_t)rows * cfg->c_dim, act, c2, stream));
     bsi_gemm_args g3{};
     g3.A = c2; g3.W = w->film_w; g3.bias = w->film_b; g3.out = film; g3.M = rows; g3.N = d.nblocks * 2 * cfg->dim; g3.K = cfg->c_dim;
     g3.lda = cfg->c_dim; g3.ldw = cfg->c_dim; g3.ldo = g3.N; g3.epilogue = BSI_EPI_BIAS_F32;
@@ -163,6 +178,8 @@ extern "C" int bsi_unet_forward(const bsi_unet_config* cfg, const bsi_unet_weigh
     const int dim = cfg->dim, H = cfg->H, W = cfg->W, L = cfg->levels;
     BSI_CHECK_ARG(dim % 32 == 0 && (dim == 64 || dim == 128) && dim % cfg->heads == 0 && (d.dh == 64 || d.dh == 128) && d.HW % 64 == 0,
                   "bsi_unet_forward: unsupported geometry dim=%d heads=%d HW=%d", dim, cfg->heads, d.HW);
+    const int act = unet_actfn(w);  // residual_block.py:41-47: after layers.0 (GroupNorm) and the FiLM stage
+    BSI_CHECK_ARG(act > 0, "bsi_unet_forward: unknown activation code %d", w->actfn);
     BSI_CHECK_ARG(cfg->block_heads == 0 || (cfg->block_heads > 0 && dim == 32 * cfg->block_heads),
                   "bsi_unet_forward: per-block attention needs head dim 32 (dim=%d, block_heads=%d)", dim, cfg->block_heads);
     for (int i = 0; cfg->block_heads > 0 && i < d.nblocks; ++i)
@@ -185,13 +202,13 @@ extern "C" int bsi_unet_forward(const bsi_unet_config* cfg, const bsi_unet_weigh
     auto part_of = [&](const float* map) -> float* {
         return gn_fuse ? reinterpret_cast<float*>(reinterpret_cast<char*>(const_cast<float*>(map)) + ws.map_bytes) : nullptr;
     };
-    auto groupnorm = [&](const float* x1, const float* x2, int cin2, const float* gw, const float* gb, int silu, void* raw) -> int {
+    auto groupnorm = [&](const float* x1, const float* x2, int cin2, const float* gw, const float* gb, int gact, void* raw) -> int {
         if (gn_fuse)
-            return bsi_groupnorm_apply_nhwc(x1, dim, part_of(x1), x2, cin2, x2 ? part_of(x2) : nullptr, B, d.HW, gw, gb, 1e-5f, silu, ws.a, raw,
+            return bsi_groupnorm_apply_nhwc(x1, dim, part_of(x1), x2, cin2, x2 ? part_of(x2) : nullptr, B, d.HW, gw, gb, 1e-5f, gact, ws.a, raw,
                                             nullptr, stream);
-        return bsi_groupnorm_nhwc(x1, dim, x2, cin2, B, d.HW, gw, gb, 1e-5f, silu, ws.a, raw, stream);
+        return bsi_groupnorm_nhwc(x1, dim, x2, cin2, B, d.HW, gw, gb, 1e-5f, gact, ws.a, raw, stream);
     };
-    // residual block (residual_block.py:61-64): out = skip(x) + conv2(silu(film(conv1(silu(gn(x))))))
+    // residual block (residual_block.py:61-64): out = skip(x) + conv2(act(film(conv1(act(gn(x))))))
     // skip_level >= 0 (gn_split): x1 IS skip tensor `skip_level`; its pass also writes the skip half of that level's up block.
     // up_level >= 0: an up block, x2 = skip tensor `up_level`.
     // block_heads > 0: the block's output goes to ws.bmap and its Residual(GroupNorm -> Attention2D) (residual_block.py:50-64) writes
@@ -205,7 +222,7 @@ extern "C" int bsi_unet_forward(const bsi_unet_config* cfg, const bsi_unet_weigh
             if (up_level >= 0) {  // the x half of cat(x, skip): groups of 8 channels, columns 0 .. dim of the level's buffers
                 char* ua = ws.upa + (size_t)up_level * ws.up_bytes;
                 char* ur = ws.upraw + (size_t)up_level * ws.up_bytes;
-                TRY(bsi_groupnorm_apply_split(x1, part_of(x1), B, d.HW, 1e-5f, GnTarget{ua, ur, rb.gn_w, rb.gn_b, 2 * dim, 0, 8, 1}, GnTarget{}, stream));
+                TRY(bsi_groupnorm_apply_split(x1, part_of(x1), B, d.HW, 1e-5f, GnTarget{ua, ur, rb.gn_w, rb.gn_b, 2 * dim, 0, 8, act}, GnTarget{}, stream));
                 a_in = ua;
                 raw_in = ur;
             } else {
@@ -213,29 +230,29 @@ extern "C" int bsi_unet_forward(const bsi_unet_config* cfg, const bsi_unet_weigh
                 if (skip_level >= 0) {  // skip tensor j is popped by up iteration L - 1 - j = block L + 2 + (L - 1 - j)
                     const bsi_unet_resblock_weights& ub = w->blocks[L + 2 + (L - 1 - skip_level)];
                     second = GnTarget{ws.upa + (size_t)skip_level * ws.up_bytes, ws.upraw + (size_t)skip_level * ws.up_bytes, ub.gn_w + dim, ub.gn_b + dim,
-                                      2 * dim, dim, 8, 1};
+                                      2 * dim, dim, 8, act};
                 }
-                TRY(bsi_groupnorm_apply_split(x1, part_of(x1), B, d.HW, 1e-5f, GnTarget{ws.a, nullptr, rb.gn_w, rb.gn_b, dim, 0, 4, 1}, second, stream));
+                TRY(bsi_groupnorm_apply_split(x1, part_of(x1), B, d.HW, 1e-5f, GnTarget{ws.a, nullptr, rb.gn_w, rb.gn_b, dim, 0, 4, act}, second, stream));
             }
         } else {
-            TRY(groupnorm(x1, x2, cin2, rb.gn_w, rb.gn_b, 1, x2 ? ws.raw : nullptr));
+            TRY(groupnorm(x1, x2, cin2, rb.gn_w, rb.gn_b, act, x2 ? ws.raw : nullptr));
         }
-        // conv1 with the FiLM + SiLU epilogue of the slab kernel (one image per wave: the (scale, shift) coefficients are loaded once
-        // per tile); BSI_UNET_SPLIT_FILM=1 keeps conv1 -> bf16 + a separate FiLM/SiLU pass for comparison
+        // conv1 with the FiLM + activation epilogue of the slab kernel (one image per wave: the (scale, shift) coefficients are loaded
+        // once per tile); BSI_UNET_SPLIT_FILM=1 keeps conv1 -> bf16 + a separate FiLM/activation pass for comparison
         static const bool split_film = getenv("BSI_UNET_SPLIT_FILM") != nullptr;
         if (split_film || d.HW % 128 != 0) {
             TRY(conv(a_in, nullptr, rb.conv1_w, rb.conv1_b, ws.zeros, ws.h1, nullptr, 0, 0, nullptr, B, H, W, dim + cin2, 0, dim, 9,
                      BSI_CONV_BIAS_BF16, stream));
-            TRY(bsi_film_silu_drop(ws.h1, (int)d.M, dim, d.HW, film + (size_t)blk * 2 * dim, film_rows, fstride, DropCfg{}, ws.y, stream));
+            TRY(bsi_film_act_drop(ws.h1, (int)d.M, dim, d.HW, film + (size_t)blk * 2 * dim, film_rows, fstride, act, DropCfg{}, ws.y, stream));
         } else {
             TRY(conv(a_in, nullptr, rb.conv1_w, rb.conv1_b, ws.zeros, ws.y, film + (size_t)blk * 2 * dim, film_rows, fstride, nullptr, B, H, W,
-                     dim + cin2, 0, dim, 9, BSI_CONV_FILM_SILU_BF16, stream));
+                     dim + cin2, 0, dim, 9, BSI_CONV_FILM_SILU_BF16, stream, nullptr, act));
         }
         // conv2 (+ the 1x1 skip conv of cat(x, x_skip) folded in as extra K steps; its bias is folded into conv2_b)
         return conv(ws.y, x2 ? raw_in : nullptr, rb.conv2_w, rb.conv2_b, ws.zeros, dst, nullptr, 0, 0, x2 ? nullptr : x1, B, H, W, dim,
                     x2 ? 2 * dim : 0, dim, 9, BSI_CONV_BIAS_RESID_F32, stream, part_of(dst));
     };
-    // x + to_out(SDPA(to_qkv(GroupNorm(x))))  (attention.py:32-41): GroupNorm without SiLU, no dropout on the attention weights
+    // x + to_out(SDPA(to_qkv(GroupNorm(x))))  (attention.py:32-41): GroupNorm without activation, no dropout on the attention weights
     auto attention = [&](const float* x, const float* gw, const float* gb, const void* qkv_w, const float* qkv_b, const void* out_w,
                          const float* out_b, int heads, float* dst) -> int {
         TRY(groupnorm(x, nullptr, 0, gw, gb, 0, nullptr));

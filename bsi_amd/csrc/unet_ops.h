@@ -2,14 +2,15 @@
 #pragma once
 #include "common.h"
 
-int bsi_film_silu_drop(const void* h1, int M, int N, int HW, const float* film, int film_rows, int film_stride, DropCfg dc,
-                       void* y, bsi_stream_t stream);
-int bsi_film_silu_bwd_drop(const void* dy, const void* h1, int M, int N, int HW, const float* film, int film_rows,
-                           int film_stride, DropCfg dc, void* dh1, float* dfilm, int dfilm_stride, bsi_stream_t stream,
+// FiLM + activation act (BSI_ACT_*) + dropout, forward and backward (bsi_film_act, bsi_film_act_bwd with a prepared DropCfg)
+int bsi_film_act_drop(const void* h1, int M, int N, int HW, const float* film, int film_rows, int film_stride, int act, DropCfg dc,
+                      void* y, bsi_stream_t stream);
+int bsi_film_act_bwd_drop(const void* dy, const void* h1, int M, int N, int HW, const float* film, int film_rows,
+                          int film_stride, int act, DropCfg dc, void* dh1, float* dfilm, int dfilm_stride, bsi_stream_t stream,
                            size_t part_stride = 0);
 // reproducible forms of the C-ABI entries that accumulate with atomics (scratch from the engine's workspace, outputs WRITTEN)
 int bsi_groupnorm_bwd_cast_det(const void* da, const float* x1, int C1, const float* x2, int C2, int B, int HW, const float* gamma,
-                               const float* beta, float eps, int silu, const float* add, const float* add_b, float* out1, float* out2,
+                               const float* beta, float eps, int act, const float* add, const float* add_b, float* out1, float* out2,
                                float* dgamma, float* dbeta, void* out1_bf16, const float* stats, float* partials, bsi_stream_t stream);
 size_t bsi_unet_decode_bwd_parts_floats(int M, int C, int Cout);
 int bsi_unet_decode_bwd_det(const float* g_xhat, const float* c_out, int coef_stride, const float* h, int B, int HW, int C, const float* w,
@@ -31,7 +32,9 @@ struct GnTarget {
     void* raw;
     const float* gamma;  // [128], already offset to this half's channels
     const float* beta;
-    int ld, col0, cpg, silu;
+    int ld, col0, cpg, act;  // act: BSI_ACT_* after the normalisation (0 none); two targets name the same one or none
 };
 int bsi_groupnorm_apply_split(const float* x, const float* part, int B, int HW, float eps, GnTarget first, GnTarget second /* out == NULL: none */,
                               bsi_stream_t stream);
+// bsi_unet_weights::actfn resolved (0 reads as SiLU); -1 for an unknown code (unet_engine.hip)
+int unet_actfn(const bsi_unet_weights* w);

@@ -1,5 +1,5 @@
 // Memory-bound kernels of the VDM-UNet path (bsi/models/vdm_unet.py, bsi/nn/residual_block.py of the reference):
-// GroupNorm(32) (+ SiLU) producer for the convolutions' A operand, the 1x1 decode convolution fused with the
+// GroupNorm(32) (+ activation) producer for the convolutions' A operand, the 1x1 decode convolution fused with the
 // preconditioning epilogue, NCHW <-> NHWC helpers.
 #include <math.h>
 
@@ -9,14 +9,28 @@
 
 namespace {
 
+// The activation of the GroupNorm outputs (residual_block.py:41-42: Norm, then ActFn).  ACT_FLAG: the run-time flag `silu` (0 none,
+// 1 SiLU) as these kernels always had it; another code: that activation (the flag is ignored).  The other GroupNorm kernels spell
+// the same choice out in place: that keeps their SiLU instantiations' code (register allocation included) what it was.
+template <int ACT>
+__device__ __forceinline__ float gn_act(float y, int silu) {
+    if constexpr (ACT == ACT_FLAG) {
+        if (silu) y = y / (1.0f + __expf(-y));
+        return y;
+    } else {
+        return act_f<ACT>(y);
+    }
+}
+
 // GroupNorm over one image (H*W pixels x C channels, NHWC fp32; optionally the channel-concatenation of two tensors,
-// simplified_unet.py:45-46 `cat((x, x_skip), dim=-3)`), 32 groups, affine, optional SiLU  ->  bf16 NHWC.
+// simplified_unet.py:45-46 `cat((x, x_skip), dim=-3)`), 32 groups, affine, optional activation (gn_act)  ->  bf16 NHWC.
 // Groups are independent, so the grid is (image, 32-channel slice): one workgroup of 256 threads normalises the 32/cpg
 // groups of its slice (B*C/32 workgroups fill the chip also at small batch).  Thread t owns the float4 channel chunk
 // (t % 8) of pixels t / 8 + k*32: a wave-instruction covers 8 pixels x 128 B (whole cache lines).
 // Two passes over the image (statistics, then normalise); `raw` optionally receives the un-normalised bf16 copy
 // (A operand of the 1x1 skip convolution, residual_block.py:40).
 constexpr int GN_CS = 32, GN_TPB = 256;  // channels per slice, threads per workgroup
+template <int ACT>
 __global__ __launch_bounds__(GN_TPB) void groupnorm_kernel(const float* __restrict__ x1, int C1, const float* __restrict__ x2,
                                                          int C2, int HW, const float* __restrict__ gamma,
                                                          const float* __restrict__ beta, float eps, int silu,
@@ -66,7 +80,11 @@ __global__ __launch_bounds__(GN_TPB) void groupnorm_kernel(const float* __restri
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             y[k] = __fmaf_rn((v[k] - mean[k]) * rstd[k], ga[k], be[k]);
-            if (silu) y[k] = y[k] / (1.0f + __expf(-y[k]));
+            if constexpr (ACT == ACT_FLAG) {
+                if (silu) y[k] = y[k] / (1.0f + __expf(-y[k]));
+            } else {
+                y[k] = act_f<ACT>(y[k]);
+            }
         }
         const size_t o = ((size_t)b * HW + p) * C + c0;
         u32x2 w;
@@ -87,7 +105,7 @@ __global__ __launch_bounds__(GN_TPB) void groupnorm_kernel(const float* __restri
 // sees one read and one write per element: (4 + 2) B/element instead of (8 + 2).  The variance is taken about the mean
 // from the registers (second LDS reduction), which is also the better-conditioned formula.
 constexpr int GN_RTPB = 1024;  // threads per workgroup
-template <int CS, int GN_RP>     // channels per slice, pixel rows per thread: CS/4 * GN_RP * ... = 1024 pixels x CS channels
+template <int CS, int GN_RP, int ACT>  // channels per slice, pixel rows per thread: CS/4 * GN_RP * ... = 1024 pixels x CS channels
 __global__ __launch_bounds__(GN_RTPB) void groupnorm_reg_kernel(const float* __restrict__ x1, int C1, const float* __restrict__ x2,
                                                              int C2, int HW, const float* __restrict__ gamma,
                                                              const float* __restrict__ beta, float eps, int silu,
@@ -170,7 +188,11 @@ __global__ __launch_bounds__(GN_RTPB) void groupnorm_reg_kernel(const float* __r
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             y[e] = __fmaf_rn((v[k][e] - mean[e]) * rstd[e], ga[e], be[e]);
-            if (silu) y[e] = y[e] / (1.0f + __expf(-y[e]));
+            if constexpr (ACT == ACT_FLAG) {
+                if (silu) y[e] = y[e] / (1.0f + __expf(-y[e]));
+            } else {
+                y[e] = act_f<ACT>(y[e]);
+            }
         }
         const size_t o = ((size_t)b * HW + p) * C + c0;
         u32x2 w;
@@ -192,7 +214,7 @@ __global__ __launch_bounds__(GN_RTPB) void groupnorm_reg_kernel(const float* __r
 // partials per group (fixed order, Chan et al.'s pairwise update: deterministic), then every thread owns ONE 4-channel column
 // quad (its mean / rstd / gamma / beta stay in registers) and walks the pixels with 8 independent 16-B loads in flight.
 constexpr int GA_TPB = 256, GA_PIX = 128;
-template <int C>  // channels of cat(x1, x2): 128 or 256
+template <int C, int ACT>  // channels of cat(x1, x2): 128 or 256
 __global__ __launch_bounds__(GA_TPB) void groupnorm_apply_kernel(const float* __restrict__ x1, int C1, const float* __restrict__ part1,
                                                                  const float* __restrict__ x2, const float* __restrict__ part2, int HW,
                                                                  const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
@@ -248,7 +270,11 @@ __global__ __launch_bounds__(GA_TPB) void groupnorm_apply_kernel(const float* __
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 y[e] = __fmaf_rn((v[u][e] - mean) * rstd, ga[e], be[e]);
-                if (silu) y[e] = y[e] / (1.0f + __expf(-y[e]));
+                if constexpr (ACT == ACT_FLAG) {
+                    if (silu) y[e] = y[e] / (1.0f + __expf(-y[e]));
+                } else {
+                    y[e] = act_f<ACT>(y[e]);
+                }
             }
             const size_t o = (pix0 + prow + (k0 + u) * PPI) * C + c0;
             u32x2 w;
@@ -371,7 +397,7 @@ extern "C" int bsi_conv_weight_pack_batch(const bsi_conv_pack_desc* descs, int n
 }
 
 static int groupnorm_impl(const float* x1, int C1, const float* x2, int C2, int B, int HW, const float* gamma, const float* beta, float eps,
-                          int silu, void* out_bf16, void* raw_bf16, float* stats, bsi_stream_t stream) {
+                          int act, void* out_bf16, void* raw_bf16, float* stats, bsi_stream_t stream) {
     BSI_CHECK_ARG(x1 && gamma && beta && out_bf16 && B > 0 && HW > 0, "bsi_groupnorm_nhwc: bad args");
     const int C = C1 + C2;
     BSI_CHECK_ARG((C == 128 || C == 256 || C == 64) && C1 % 32 == 0 && C2 % 32 == 0 && (C2 == 0 || x2),
@@ -379,33 +405,38 @@ static int groupnorm_impl(const float* x1, int C1, const float* x2, int C2, int 
     BSI_CHECK_ARG(!stats || HW <= 1024, "bsi_groupnorm_stats_nhwc: statistics output needs H*W <= 1024");
     __bf16* o = reinterpret_cast<__bf16*>(out_bf16);
     __bf16* r = reinterpret_cast<__bf16*>(raw_bf16);
-    if (HW <= 1024 && C1 % 64 == 0 && C2 % 64 == 0)  // 64-channel slices: whole 128-B lines of bf16 output (measured 60 / 126 us vs 67 / 154)
-        hipLaunchKernelGGL((groupnorm_reg_kernel<64, 16>), dim3(B, C / 64), dim3(GN_RTPB), 0, S(stream), x1, C1, x2, C2, HW, gamma, beta, eps,
-                           silu, o, r, stats);
-    else if (HW <= 1024)
-        hipLaunchKernelGGL((groupnorm_reg_kernel<32, 8>), dim3(B, C / 32), dim3(GN_RTPB), 0, S(stream), x1, C1, x2, C2, HW, gamma, beta, eps,
-                           silu, o, r, stats);
-    else
-        hipLaunchKernelGGL(groupnorm_kernel, dim3(B, C / GN_CS), dim3(GN_TPB), 0, S(stream), x1, C1, x2, C2, HW, gamma, beta, eps, silu, o, r);
-    BSI_CHECK_LAUNCH("bsi_groupnorm_nhwc");
-    return BSI_OK;
+    return bsi_with_act_flag(act, "bsi_groupnorm_nhwc", [&](auto a) {
+        constexpr int ACT = decltype(a)::value;
+        const int silu = act;  // the flag of the ACT_FLAG instantiation
+        if (HW <= 1024 && C1 % 64 == 0 && C2 % 64 == 0)  // 64-channel slices: whole 128-B lines of bf16 output (measured 60 / 126 us vs 67 / 154)
+            hipLaunchKernelGGL((groupnorm_reg_kernel<64, 16, ACT>), dim3(B, C / 64), dim3(GN_RTPB), 0, S(stream), x1, C1, x2, C2, HW, gamma, beta,
+                               eps, silu, o, r, stats);
+        else if (HW <= 1024)
+            hipLaunchKernelGGL((groupnorm_reg_kernel<32, 8, ACT>), dim3(B, C / 32), dim3(GN_RTPB), 0, S(stream), x1, C1, x2, C2, HW, gamma, beta,
+                               eps, silu, o, r, stats);
+        else
+            hipLaunchKernelGGL(groupnorm_kernel<ACT>, dim3(B, C / GN_CS), dim3(GN_TPB), 0, S(stream), x1, C1, x2, C2, HW, gamma, beta, eps, silu,
+                               o, r);
+        BSI_CHECK_LAUNCH("bsi_groupnorm_nhwc");
+        return BSI_OK;
+    });
 }
 
 extern "C" int bsi_groupnorm_nhwc(const float* x1, int C1, const float* x2, int C2, int B, int HW, const float* gamma,
-                                  const float* beta, float eps, int silu, void* out_bf16, void* raw_bf16,
+                                  const float* beta, float eps, int act, void* out_bf16, void* raw_bf16,
                                   bsi_stream_t stream) {
-    return groupnorm_impl(x1, C1, x2, C2, B, HW, gamma, beta, eps, silu, out_bf16, raw_bf16, nullptr, stream);
+    return groupnorm_impl(x1, C1, x2, C2, B, HW, gamma, beta, eps, act, out_bf16, raw_bf16, nullptr, stream);
 }
 
 extern "C" int bsi_groupnorm_stats_nhwc(const float* x1, int C1, const float* x2, int C2, int B, int HW, const float* gamma,
-                                        const float* beta, float eps, int silu, void* out_bf16, void* raw_bf16, float* stats,
+                                        const float* beta, float eps, int act, void* out_bf16, void* raw_bf16, float* stats,
                                         bsi_stream_t stream) {
     BSI_CHECK_ARG(stats, "bsi_groupnorm_stats_nhwc: statistics pointer missing");
-    return groupnorm_impl(x1, C1, x2, C2, B, HW, gamma, beta, eps, silu, out_bf16, raw_bf16, stats, stream);
+    return groupnorm_impl(x1, C1, x2, C2, B, HW, gamma, beta, eps, act, out_bf16, raw_bf16, stats, stream);
 }
 
 extern "C" int bsi_groupnorm_apply_nhwc(const float* x1, int C1, const float* part1, const float* x2, int C2, const float* part2, int B,
-                                        int HW, const float* gamma, const float* beta, float eps, int silu, void* out_bf16,
+                                        int HW, const float* gamma, const float* beta, float eps, int act, void* out_bf16,
                                         void* raw_bf16, float* stats, bsi_stream_t stream) {
     BSI_CHECK_ARG(x1 && part1 && gamma && beta && out_bf16 && B > 0 && HW > 0, "bsi_groupnorm_apply_nhwc: bad args");
     const int C = C1 + C2;
@@ -415,18 +446,26 @@ extern "C" int bsi_groupnorm_apply_nhwc(const float* x1, int C1, const float* pa
     __bf16* o = reinterpret_cast<__bf16*>(out_bf16);
     __bf16* r = reinterpret_cast<__bf16*>(raw_bf16);
     const dim3 grid(B, HW / GA_PIX);
-    if (C == 128)
-        hipLaunchKernelGGL(groupnorm_apply_kernel<128>, grid, dim3(GA_TPB), 0, S(stream), x1, C1, part1, x2, part2, HW, gamma, beta, eps, silu, o, r, stats);
-    else
-        hipLaunchKernelGGL(groupnorm_apply_kernel<256>, grid, dim3(GA_TPB), 0, S(stream), x1, C1, part1, x2, part2, HW, gamma, beta, eps, silu, o, r, stats);
-    BSI_CHECK_LAUNCH("bsi_groupnorm_apply_nhwc");
-    return BSI_OK;
+    return bsi_with_act_flag(act, "bsi_groupnorm_apply_nhwc", [&](auto a) {
+        constexpr int ACT = decltype(a)::value;
+        const int silu = act;
+        if (C == 128)
+            hipLaunchKernelGGL((groupnorm_apply_kernel<128, ACT>), grid, dim3(GA_TPB), 0, S(stream), x1, C1, part1, x2, part2, HW, gamma, beta, eps,
+                               silu, o, r, stats);
+        else
+            hipLaunchKernelGGL((groupnorm_apply_kernel<256, ACT>), grid, dim3(GA_TPB), 0, S(stream), x1, C1, part1, x2, part2, HW, gamma, beta, eps,
+                               silu, o, r, stats);
+        BSI_CHECK_LAUNCH("bsi_groupnorm_apply_nhwc");
+        return BSI_OK;
+    });
 }
 
 // See unet_ops.h (bsi_groupnorm_apply_split).  Same streaming structure as groupnorm_apply_kernel<128>: workgroup = 128 pixels of one
 // image, a thread owns one 4-channel quad; the statistics of BOTH groupings (4- and 8-channel groups) come from the same partials.
-struct GnTargetDev { __bf16* out; __bf16* raw; const float* gamma; const float* beta; int ld, col0, silu; };
-template <int CPG1, int CPG2>  // channels per group of the two targets (CPG2 = 0: one target)
+struct GnTargetDev { __bf16* out; __bf16* raw; const float* gamma; const float* beta; int ld, col0, act; };
+// A target's `act` is its activation code (0: none); with ACT != ACT_FLAG every target with a non-zero code applies ACT (the launcher checks
+// that they name the same one).
+template <int CPG1, int CPG2, int ACT>  // channels per group of the two targets (CPG2 = 0: one target)
 __global__ __launch_bounds__(GA_TPB) void groupnorm_apply_split_kernel(const float* __restrict__ x, const float* __restrict__ part, int HW, float eps,
                                                                        GnTargetDev t1, GnTargetDev t2) {
     constexpr int C = 128, Q = C / 4, PPI = GA_TPB / Q;  // 32 quads per pixel, 8 pixels per trip
@@ -468,7 +507,8 @@ __global__ __launch_bounds__(GA_TPB) void groupnorm_apply_split_kernel(const flo
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             y[e] = __fmaf_rn((v[e] - mean) * rstd, ga[e], be[e]);
-            if (tg.silu) y[e] = y[e] / (1.0f + __expf(-y[e]));
+            if constexpr (ACT == ACT_FLAG) y[e] = gn_act<ACT>(y[e], tg.act);
+            else if (tg.act) y[e] = act_f<ACT>(y[e]);
         }
         const size_t o = pix * tg.ld + tg.col0 + c0;
         u32x2 w;
@@ -503,16 +543,25 @@ int bsi_groupnorm_apply_split(const float* x, const float* part, int B, int HW, 
                       (!second.out || (second.gamma && second.beta && second.ld % 4 == 0 && second.col0 % 4 == 0)),
                   "bsi_groupnorm_apply_split: unsupported grouping / layout");
     auto dev = [](const GnTarget& g) {
-        return GnTargetDev{reinterpret_cast<__bf16*>(g.out), reinterpret_cast<__bf16*>(g.raw), g.gamma, g.beta, g.ld, g.col0, g.silu};
+        return GnTargetDev{reinterpret_cast<__bf16*>(g.out), reinterpret_cast<__bf16*>(g.raw), g.gamma, g.beta, g.ld, g.col0, g.act};
     };
     const dim3 grid(B, HW / GA_PIX);
     const GnTargetDev a = dev(first), b = dev(second);
-    if (second.out && first.cpg == 4) hipLaunchKernelGGL((groupnorm_apply_split_kernel<4, 8>), grid, dim3(GA_TPB), 0, S(stream), x, part, HW, eps, a, b);
-    else if (second.out) hipLaunchKernelGGL((groupnorm_apply_split_kernel<8, 8>), grid, dim3(GA_TPB), 0, S(stream), x, part, HW, eps, a, b);
-    else if (first.cpg == 4) hipLaunchKernelGGL((groupnorm_apply_split_kernel<4, 0>), grid, dim3(GA_TPB), 0, S(stream), x, part, HW, eps, a, b);
-    else hipLaunchKernelGGL((groupnorm_apply_split_kernel<8, 0>), grid, dim3(GA_TPB), 0, S(stream), x, part, HW, eps, a, b);
-    BSI_CHECK_LAUNCH("bsi_groupnorm_apply_split");
-    return BSI_OK;
+    // each target: no activation (0) or the launch's one
+    const int act = second.out && second.act > first.act ? second.act : first.act;
+    BSI_CHECK_ARG((first.act == 0 || first.act == act) && (!second.out || second.act == 0 || second.act == act),
+                  "bsi_groupnorm_apply_split: the targets' activations %d, %d differ", first.act, second.act);
+    return bsi_with_act_flag(act, "bsi_groupnorm_apply_split", [&](auto ac) {
+        constexpr int ACT = decltype(ac)::value;
+        if (second.out && first.cpg == 4)
+            hipLaunchKernelGGL((groupnorm_apply_split_kernel<4, 8, ACT>), grid, dim3(GA_TPB), 0, S(stream), x, part, HW, eps, a, b);
+        else if (second.out) hipLaunchKernelGGL((groupnorm_apply_split_kernel<8, 8, ACT>), grid, dim3(GA_TPB), 0, S(stream), x, part, HW, eps, a, b);
+        else if (first.cpg == 4)
+            hipLaunchKernelGGL((groupnorm_apply_split_kernel<4, 0, ACT>), grid, dim3(GA_TPB), 0, S(stream), x, part, HW, eps, a, b);
+        else hipLaunchKernelGGL((groupnorm_apply_split_kernel<8, 0, ACT>), grid, dim3(GA_TPB), 0, S(stream), x, part, HW, eps, a, b);
+        BSI_CHECK_LAUNCH("bsi_groupnorm_apply_split");
+        return BSI_OK;
+    });
 }
 
 extern "C" int bsi_unet_decode(const float* h, int B, int HW, int C, const float* w, const float* bias, int Cout,

@@ -3,16 +3,14 @@
 // bsi/nn/attention.py:32-41 of the reference in `BSI.train_loss(...).mean().backward()`, bsi/tasks/bsi.py:187-194).
 // Host-side sequencing only; no allocation, no synchronisation.
 //
-// Tape per residual block and pixel: a = bf16 silu(GN(x)) [Cx], (up blocks: raw = bf16 x [2 dim]), h1 = bf16 conv1 output
-// [dim], y = bf16 dropout(silu(film(h1))) [dim], out fp32 [dim]  = 1.25 MB (2 MB for an up block) per 32x32 image at
+// Tape per residual block and pixel: a = bf16 act(GN(x)) [Cx], (up blocks: raw = bf16 x [2 dim]), h1 = bf16 conv1 output
+// [dim], y = bf16 dropout(act(film(h1))) [dim], out fp32 [dim]  = 1.25 MB (2 MB for an up block) per 32x32 image at
 // dim 128: 109 MB per image for the 67-block UNet of config/experiment/cifar10-vdm.yaml, 14 GB at 128 images per GPU.
 // With per-block attention (block_heads > 0) every block adds its Residual(GroupNorm -> Attention2D) tape: the stage's fp32 input,
 // bf16 GroupNorm output, qkv and attention output, the LSE and a GroupNorm statistics slot (+1.75 MB per block and 32x32 image).
 #include "common.h"
 #include "dit_ops.h"
 #include "unet_ops.h"
-
-extern "C" int bsi_silu_bf16(const float* pre, size_t n, void* out, bsi_stream_t stream);
 
 namespace {
 
@@ -261,6 +259,8 @@ extern "C" int bsi_unet_train_forward(const bsi_unet_config* cfg, const bsi_unet
                   "bsi_unet_train_forward: c_in/c_skip/c_out must be given together");
     const UD d = ud(cfg, B);
     TRY(check_geometry(cfg, d, "bsi_unet_train_forward"));
+    const int act = unet_actfn(w);  // pos_map.2,4 and residual_block.py layers.1,4
+    BSI_CHECK_ARG(act > 0, "bsi_unet_train_forward: unknown activation code %d", w->actfn);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const int dim = d.dim, H = cfg->H, W = cfg->W, L = d.L, M = (int)d.M, cd = cfg->c_dim;
     UTape tp = carve_tape(cfg, B, tape_mem);
@@ -274,9 +274,9 @@ extern "C" int bsi_unet_train_forward(const bsi_unet_config* cfg, const bsi_unet
         TRY(bsi_nyquist_embed(t, B, w->pe_scale, w->pe_bias, cfg->emb_size, embf, nullptr, stream));
         TRY(bsi_cast_rows_bf16(embf, cfg->emb_size, B, cfg->emb_size, tp.emb, 64, stream));
         TRY(gemm(tp.emb, 64, w->pm1_w, 64, w->pm1_b, tp.pre1, cd, B, cd, 64, BSI_EPI_BIAS_F32, stream));
-        TRY(bsi_silu_bf16(tp.pre1, (size_t)B * cd, tp.c1, stream));
+        TRY(bsi_act_bf16(tp.pre1, (size_t)B * cd, act, tp.c1, stream));
         TRY(gemm(tp.c1, cd, w->pm3_w, cd, w->pm3_b, tp.pre2, cd, B, cd, cd, BSI_EPI_BIAS_F32, stream));
-        TRY(bsi_silu_bf16(tp.pre2, (size_t)B * cd, tp.c2, stream));
+        TRY(bsi_act_bf16(tp.pre2, (size_t)B * cd, act, tp.c2, stream));
         TRY(gemm(tp.c2, cd, w->film_w, cd, w->film_b, tp.film, d.F, B, d.F, cd, BSI_EPI_BIAS_F32, stream));
     }
     TRY(bsi_dit_prologue_launch(mu, c_in, 1, B, cfg->C, H, W, 1, cfg->ff_nmin, d.nfreq, d.cin_pad, tp.xin, s));
@@ -286,15 +286,15 @@ extern "C" int bsi_unet_train_forward(const bsi_unet_config* cfg, const bsi_unet
     static const bool no_gn_fuse = getenv("BSI_UNET_NO_GN_FUSE") != nullptr;
     const bool gn_fuse = !no_gn_fuse && dim == 128 && d.HW % 128 == 0 && d.HW <= 1024;
     auto part = [&](int slot) -> float* { return gn_fuse ? tp.gnpart + (size_t)slot * tp.gnpart_stride : nullptr; };
-    auto groupnorm = [&](const float* x1, int x1p, const float* x2, int x2p, const float* gw, const float* gb, int silu, void* a, void* raw,
+    auto groupnorm = [&](const float* x1, int x1p, const float* x2, int x2p, const float* gw, const float* gb, int gact, void* a, void* raw,
                          float* stats) -> int {
         const int cin2 = x2 ? dim : 0;
         if (gn_fuse)
-            return bsi_groupnorm_apply_nhwc(x1, dim, part(x1p), x2, cin2, x2 ? part(x2p) : nullptr, B, d.HW, gw, gb, 1e-5f, silu, a, raw, stats,
+            return bsi_groupnorm_apply_nhwc(x1, dim, part(x1p), x2, cin2, x2 ? part(x2p) : nullptr, B, d.HW, gw, gb, 1e-5f, gact, a, raw, stats,
                                             stream);
         if (d.HW <= 1024)  // the register-resident kernel also saves (mean, rstd) for the backward pass
-            return bsi_groupnorm_stats_nhwc(x1, dim, x2, cin2, B, d.HW, gw, gb, 1e-5f, silu, a, raw, stats, stream);
-        return bsi_groupnorm_nhwc(x1, dim, x2, cin2, B, d.HW, gw, gb, 1e-5f, silu, a, raw, stream);
+            return bsi_groupnorm_stats_nhwc(x1, dim, x2, cin2, B, d.HW, gw, gb, 1e-5f, gact, a, raw, stats, stream);
+        return bsi_groupnorm_nhwc(x1, dim, x2, cin2, B, d.HW, gw, gb, 1e-5f, gact, a, raw, stream);
     };
     TRY(conv(tp.xin, nullptr, w->enc_w, w->enc_b, tp.zeros, tp.henc, nullptr, B, H, W, d.cin_pad, 0, dim, 9, BSI_CONV_BIAS_RESID_F32,
              stream, part(0)));
@@ -302,11 +302,11 @@ extern "C" int bsi_unet_train_forward(const bsi_unet_config* cfg, const bsi_unet
         const bsi_unet_resblock_weights& rb = w->blocks[blk];
         BlockTape bt = block_tape(tp, d, blk);
         const int cin2 = x2 ? dim : 0;
-        TRY(groupnorm(x1, x1p, x2, x2p, rb.gn_w, rb.gn_b, 1, bt.a, x2 ? bt.raw : nullptr, tp.gnstats + (size_t)blk * B * 64));
+        TRY(groupnorm(x1, x1p, x2, x2p, rb.gn_w, rb.gn_b, act, bt.a, x2 ? bt.raw : nullptr, tp.gnstats + (size_t)blk * B * 64));
         TRY(conv(bt.a, nullptr, rb.conv1_w, rb.conv1_b, tp.zeros, bt.h1, nullptr, B, H, W, dim + cin2, 0, dim, 9, BSI_CONV_BIAS_BF16,
                  stream));
-        TRY(bsi_film_silu_drop(bt.h1, M, dim, d.HW, tp.film + (size_t)blk * 2 * dim, B, d.F, make_drop(dropout_p, seed, blk), bt.y,
-                               stream));
+        TRY(bsi_film_act_drop(bt.h1, M, dim, d.HW, tp.film + (size_t)blk * 2 * dim, B, d.F, act, make_drop(dropout_p, seed, blk), bt.y,
+                              stream));
         return conv(bt.y, x2 ? bt.raw : nullptr, rb.conv2_w, rb.conv2_b, tp.zeros, dst, x2 ? nullptr : x1, B, H, W, dim,
                     x2 ? 2 * dim : 0, dim, 9, BSI_CONV_BIAS_RESID_F32, stream, part(dstp));
     };
@@ -362,6 +362,8 @@ extern "C" int bsi_unet_backward(const bsi_unet_config* cfg, const bsi_unet_weig
     BSI_CHECK_ARG(dropout_p >= 0.f && dropout_p < 1.f, "bsi_unet_backward: dropout probability %g outside [0, 1)", (double)dropout_p);
     const UD d = ud(cfg, B);
     TRY(check_geometry(cfg, d, "bsi_unet_backward"));
+    const int act = unet_actfn(w);
+    BSI_CHECK_ARG(act > 0, "bsi_unet_backward: unknown activation code %d", w->actfn);
     const int dim = d.dim, H = cfg->H, W = cfg->W, L = d.L, M = (int)d.M, cd = cfg->c_dim;
     UTape tp = carve_tape(cfg, B, tape_mem);
     UBwd ws = carve_bwd(cfg, B, workspace);
@@ -387,8 +389,8 @@ extern "C" int bsi_unet_backward(const bsi_unet_config* cfg, const bsi_unet_weig
         TRY(bsi_conv_wgrad_conv2d_nhwc_bf16(ws.g, dim, bt.y, x2 ? bt.raw : nullptr, tp.zeros, B, H, W, dim, dim, x2 ? 2 * dim : 0, dim, 9,
                                             rg.conv2_w, x2 ? rg.skip_w : nullptr, rg.conv2_b, ws.wg, stream));
         TRY(conv(ws.g, nullptr, rT.conv2_wT, nullptr, tp.zeros, ws.dy, nullptr, B, H, W, dim, 0, dim, 9, BSI_CONV_BIAS_BF16, stream));
-        TRY(bsi_film_silu_bwd_drop(ws.dy, bt.h1, M, dim, d.HW, tp.film + (size_t)blk * 2 * dim, B, d.F, make_drop(dropout_p, seed, blk),
-                                   ws.dh1, ws.dfilm + (size_t)blk * 2 * dim, d.F, stream, fplane));
+        TRY(bsi_film_act_bwd_drop(ws.dy, bt.h1, M, dim, d.HW, tp.film + (size_t)blk * 2 * dim, B, d.F, act, make_drop(dropout_p, seed, blk),
+                                  ws.dh1, ws.dfilm + (size_t)blk * 2 * dim, d.F, stream, fplane));
         TRY(bsi_conv_wgrad_conv2d_nhwc_bf16(ws.dh1, dim, bt.a, nullptr, tp.zeros, B, H, W, cx, cx, 0, dim, 9, rg.conv1_w, nullptr, rg.conv1_b,
                                             ws.wg, stream));
         TRY(conv(ws.dh1, nullptr, rT.conv1_wT, nullptr, tp.zeros, ws.da, nullptr, B, H, W, dim, 0, cx, 9, BSI_CONV_BIAS_BF16, stream));
@@ -400,7 +402,7 @@ extern "C" int bsi_unet_backward(const bsi_unet_config* cfg, const bsi_unet_weig
         (void)rb;
         // out1 is the next block's dOut: its bf16 copy goes straight into ws.g (no longer read by this block)
         g_ready = true;
-        return bsi_groupnorm_bwd_cast_det(ws.da, x1, dim, x2, cin2, B, d.HW, rb.gn_w, rb.gn_b, 1e-5f, 1, add, add_b, out1, out2, rg.gn_w,
+        return bsi_groupnorm_bwd_cast_det(ws.da, x1, dim, x2, cin2, B, d.HW, rb.gn_w, rb.gn_b, 1e-5f, act, add, add_b, out1, out2, rg.gn_w,
                                           rg.gn_b, ws.g, d.HW <= 1024 ? tp.gnstats + (size_t)blk * B * 64 : nullptr, ws.gnpart, stream);
     };
 
@@ -472,10 +474,10 @@ extern "C" int bsi_unet_backward(const bsi_unet_config* cfg, const bsi_unet_weig
     TRY(bsi_sum_cast_rows_bf16(ws.dfilm, fplanes, fplane, d.F, B, d.F, ws.dfilm_bf, d.F, stream));
     TRY(bsi_gemm_tn_bias_bf16(ws.dfilm_bf, d.F, tp.c2, cd, B, d.F, cd, g->film_w, cd, g->film_b, 0, ws.tn, stream));
     TRY(gemm(ws.dfilm_bf, d.F, wT->film_wT, d.F, nullptr, ws.dc, cd, B, cd, d.F, BSI_EPI_BIAS_F32, stream));
-    TRY(bsi_silu_bwd_bf16(ws.dc, tp.pre2, (size_t)B * cd, ws.dpre_bf, stream));
+    TRY(bsi_act_bwd_bf16(ws.dc, tp.pre2, (size_t)B * cd, act, ws.dpre_bf, stream));
     TRY(bsi_gemm_tn_bias_bf16(ws.dpre_bf, cd, tp.c1, cd, B, cd, cd, g->pm3_w, cd, g->pm3_b, 0, ws.tn, stream));
     TRY(gemm(ws.dpre_bf, cd, wT->pm3_wT, cd, nullptr, ws.dc, cd, B, cd, cd, BSI_EPI_BIAS_F32, stream));
-    TRY(bsi_silu_bwd_bf16(ws.dc, tp.pre1, (size_t)B * cd, ws.dpre_bf, stream));
+    TRY(bsi_act_bwd_bf16(ws.dc, tp.pre1, (size_t)B * cd, act, ws.dpre_bf, stream));
     TRY(bsi_gemm_tn_bf16(ws.dpre_bf, cd, tp.emb, 64, B, cd, 64, g->pm1_w_padded, 64, 0, ws.tn, stream));
     return bsi_colsum_bf16(ws.dpre_bf, cd, B, cd, g->pm1_b, 0, ws.cs, stream);
 }

@@ -3,7 +3,7 @@ sequential}.py on the native UNet engine (`bsi_unet_film` + `bsi_unet_forward`, 
 
 Module tree, constructor signature and state-dict keys are those of the reference: the torch
 submodules only HOLD the fp32 parameters; the forward is implicit-GEMM convolutions on bf16 MFMA with fused
-GroupNorm/SiLU/FiLM/residual epilogues, fused attention and an fp32 feature map between blocks."""
+GroupNorm/ActFn/FiLM/residual epilogues, fused attention and an fp32 feature map between blocks."""
 import ctypes as C
 
 import torch
@@ -76,9 +76,10 @@ class DenoisingVDMUNet(nn.Module):
         self.pos_emb = pos_emb
         self.fourier_features = fourier_features
         assert len(self.data_shape) == 3, "Only works for 2D images"
-        if actfn != "silu" or padding_mode != "zeros":
-            raise NotImplementedError("bsi_amd.DenoisingVDMUNet: the native kernels implement actfn='silu' and "
-                                      "padding_mode='zeros' (the reference's configuration)")
+        ActFn = actfn_from_str(actfn)  # KeyError for an unknown name, as in the reference
+        if padding_mode != "zeros":
+            raise NotImplementedError("bsi_amd.DenoisingVDMUNet: the native kernels implement padding_mode='zeros' (the reference's "
+                                      "configuration)")
         if downsampling_attention and dim != 128:
             raise NotImplementedError(f"bsi_amd.DenoisingVDMUNet: downsampling_attention=True needs dim=128 (the per-block "
                                       f"Attention2D has 4 heads; dim={dim} gives head dim {dim // 4}, and the native attention "
@@ -87,7 +88,6 @@ class DenoisingVDMUNet(nn.Module):
         in_features = out_features = n_channels
         if fourier_features is not None:
             in_features += n_channels * fourier_features.n_features()
-        ActFn = actfn_from_str(actfn)
 
         def Norm(c):
             return nn.GroupNorm(32, c)
@@ -110,6 +110,8 @@ class DenoisingVDMUNet(nn.Module):
         self._cfg_args = dict(dim=dim, levels=levels, heads=n_attention_heads, c_dim=c_dim,
                               block_heads=4 if downsampling_attention else 0)
         self._dropout = dropout
+        self.actfn = actfn
+        self._act_code = N.ACT_CODES[actfn]  # bsi_unet_weights.actfn: every ActFn site of the engines (no parameters, no state-dict key)
         self._pack = None
         self._pack_key = None
         self._pack_t = None
@@ -258,6 +260,7 @@ class DenoisingVDMUNet(nn.Module):
         w.aqkv_w, w.aqkv_b = conv_pack(att[1].to_qkv), f32(att[1].to_qkv.bias)
         w.aout_w, w.aout_b = conv_pack(att[1].to_out), f32(att[1].to_out.bias)
         w.blocks = C.cast(arr, C.POINTER(N.UNetResBlockWeights))
+        w.actfn = self._act_code
         darr = (N.ConvPackDesc * len(descs))(*descs)
         descs_dev = torch.frombuffer(bytearray(bytes(darr)), dtype=torch.uint8).to(dev)
         keep.extend([b2_dst, b2_tmp, film_w_cat, film_b_cat, descs_dev, film_ws, film_bs])

@@ -408,9 +408,20 @@ int bsi_dit_forward_pair(const bsi_dit_config* cfg, const bsi_dit_weights* w /*h
  * VDM-UNet building blocks — bsi/models/vdm_unet.py, bsi/nn/residual_block.py, bsi/nn/attention.py.
  * Activations are NHWC: [B*H*W pixels][channels].
  * ---------------------------------------------------------------------------------------- */
+/* Activation codes: the UNet's ActFn (actfn_from_str, bsi/models/utils.py:4-12) with torch's defaults.  The `int act` arguments of
+ * the GroupNorm entries were `int silu` flags before; 0 and 1 keep that meaning.
+ *   GELU     nn.GELU(), exact erf form 0.5*x*(1+erf(x/sqrt 2))        (not the DiT's tanh approximation)
+ *   RELU     max(x, 0); derivative 0 at x = 0
+ *   SOFTPLUS nn.Softplus(): x > 20 ? x : log1p(exp(x)); derivative x > 20 ? 1 : sigmoid(x)
+ *   TANH     tanh(x) */
+enum { BSI_ACT_NONE = 0, BSI_ACT_SILU = 1, BSI_ACT_GELU = 2, BSI_ACT_RELU = 3, BSI_ACT_SOFTPLUS = 4, BSI_ACT_TANH = 5 };
+/* out_bf16[i] = bf16(act(pre[i])) (the training engine's pos_map activations, vdm_unet.py:65-69); bsi_silu_bf16 with any code. */
+int bsi_act_bf16(const float* pre, size_t n, int act, void* out, bsi_stream_t stream);
+/* out_bf16[i] = bf16(ds[i] * act'(pre[i])); bsi_silu_bwd_bf16 with any code (pre must not be NULL). */
+int bsi_act_bwd_bf16(const float* ds, const float* pre, size_t n, int act, void* out, bsi_stream_t stream);
 enum {
     BSI_CONV_BIAS_BF16 = 0,      /* out_bf16 = bf16(conv + bias)                                   (attention.py:29) */
-    BSI_CONV_FILM_SILU_BF16 = 1, /* out_bf16 = bf16(silu((conv + bias)*(scale+1) + shift))  (residual_block.py:44-46) */
+    BSI_CONV_FILM_SILU_BF16 = 1, /* out_bf16 = bf16(act((conv + bias)*(scale+1) + shift))  (residual_block.py:44-46); act: bsi_conv_args.act */
     BSI_CONV_BIAS_RESID_F32 = 2, /* out_f32 = conv + bias (+ resid)                    (residual_block.py:48,63) */
 };
 typedef struct bsi_conv_args {
@@ -426,6 +437,7 @@ typedef struct bsi_conv_args {
     int B, H, W, Cin, Cin2, Cout, taps /* 9 = 3x3 pad 1, 1 = 1x1 */, ldo, epilogue;
     float* gn_partial; /* BIAS_RESID_F32, optional: [B*H*W/128][Cout/4][2] = (mean, M2) of every 128-pixel x 4-channel block of
                           `out`, written by the epilogue for bsi_groupnorm_apply_nhwc (needs H*W % 128 == 0, Cout % 64 == 0) */
+    int act;           /* FILM: the activation, BSI_ACT_SILU .. BSI_ACT_TANH; 0 also means SiLU (zero-initialised callers) */
 } bsi_conv_args;
 /* Conv2d(stride 1, zero padding) as implicit GEMM on bf16 MFMA; Cin, Cin2 multiples of 32, Cout of 16. */
 int bsi_conv_nhwc_bf16(const bsi_conv_args* a /*host*/, bsi_stream_t stream);
@@ -473,31 +485,32 @@ int bsi_conv_wgrad_bias_nhwc_bf16(const void* dy, int ldy, const void* x, const 
                                   void* workspace, bsi_stream_t stream);
 int bsi_conv_wgrad_unpack(const float* packed, int Cout, int Cin, int taps, int cin_pad, int ld, int col0, int accumulate,
                           float* out, bsi_stream_t stream);
-/* GroupNorm(32 groups, affine, eps) over cat(x1, x2) channels (x2 nullable) per image, optional SiLU -> bf16 NHWC
- * (residual_block.py:42-43, vdm_unet.py:52,84); raw_bf16 (nullable) receives the un-normalised bf16 copy. */
+/* GroupNorm(32 groups, affine, eps) over cat(x1, x2) channels (x2 nullable) per image, then activation `act` (BSI_ACT_*; 0 = none)
+ * -> bf16 NHWC (residual_block.py:42-43, vdm_unet.py:52,84); raw_bf16 (nullable) receives the un-normalised bf16 copy. */
 int bsi_groupnorm_nhwc(const float* x1, int C1, const float* x2, int C2, int B, int HW, const float* gamma,
-                       const float* beta, float eps, int silu, void* out_bf16, void* raw_bf16, bsi_stream_t stream);
+                       const float* beta, float eps, int act, void* out_bf16, void* raw_bf16, bsi_stream_t stream);
 /* Same, and saves (mean, rstd) of every (image, group) to stats[B][32][2] for the backward pass (H*W <= 1024). */
 int bsi_groupnorm_stats_nhwc(const float* x1, int C1, const float* x2, int C2, int B, int HW, const float* gamma, const float* beta,
-                             float eps, int silu, void* out_bf16, void* raw_bf16, float* stats, bsi_stream_t stream);
+                             float eps, int act, void* out_bf16, void* raw_bf16, float* stats, bsi_stream_t stream);
 /* The same GroupNorm as ONE streaming pass: the statistics come from the partials the producing convolutions wrote
  * (bsi_conv_args::gn_partial: part1 [B*HW/128][C1/4][2], part2 [B*HW/128][C2/4][2] = (mean, M2) of 128 pixels x 4 channels),
  * merged per (image, group) in a fixed order, so x is read once and never held.  C1 + C2 = 128 or 256, H*W % 128 == 0;
  * stats (nullable) receives (mean, rstd) as bsi_groupnorm_stats_nhwc writes them. */
 int bsi_groupnorm_apply_nhwc(const float* x1, int C1, const float* part1, const float* x2, int C2, const float* part2, int B, int HW,
-                             const float* gamma, const float* beta, float eps, int silu, void* out_bf16, void* raw_bf16,
+                             const float* gamma, const float* beta, float eps, int act, void* out_bf16, void* raw_bf16,
                              float* stats, bsi_stream_t stream);
-/* Backward of bsi_groupnorm_nhwc: da bf16 [B*HW, C1+C2] is the gradient of the (SiLU'd) output.
+/* Backward of bsi_groupnorm_nhwc: da bf16 [B*HW, C1+C2] is the gradient of the activated output (act' is taken at the
+ * recomputed pre-activation z = n*gamma + beta).
  *   out1 [B*HW, C1] = dx1 (+ add[:, :C1]) (+ add_b),  out2 [B*HW, C2] = dx2 (+ add[:, C1:]);  add: fp32 [B*HW, C1+C2] or NULL,
  *   add_b: fp32 [B*HW, C1] or NULL (out1 may alias add when C2 == 0);  dgamma, dbeta [C1+C2] are ACCUMULATED (atomics). */
 int bsi_groupnorm_bwd_nhwc(const void* da, const float* x1, int C1, const float* x2, int C2, int B, int HW,
-                           const float* gamma, const float* beta, float eps, int silu, const float* add, const float* add_b,
+                           const float* gamma, const float* beta, float eps, int act, const float* add, const float* add_b,
                            float* out1, float* out2, float* dgamma, float* dbeta, bsi_stream_t stream);
 /* Same, and also writes the x1 gradient as bf16 [B*HW, C1] (the dY operand of the next block's weight / input gradient
  * convolutions: saves a separate fp32 -> bf16 pass over it); `stats` = the (mean, rstd) pairs bsi_groupnorm_stats_nhwc saved in the
  * forward pass ([B][32][2] floats), NULL = recompute them. */
 int bsi_groupnorm_bwd_cast_nhwc(const void* da, const float* x1, int C1, const float* x2, int C2, int B, int HW, const float* gamma,
-                                const float* beta, float eps, int silu, const float* add, const float* add_b, float* out1,
+                                const float* beta, float eps, int act, const float* add, const float* add_b, float* out1,
                                 float* out2, float* dgamma, float* dbeta, void* out1_bf16, const float* stats /* or NULL */,
                                 bsi_stream_t stream);
 /* Training form of the FiLM stage (residual_block.py:21-24,44-46): y = Dropout_p(SiLU(h1*(scale+1)+shift)), h1 and y bf16
@@ -509,6 +522,13 @@ int bsi_film_silu(const void* h1, int M, int N, int HW, const float* film, int f
 int bsi_film_silu_bwd(const void* dy, const void* h1, int M, int N, int HW, const float* film, int film_rows, int film_stride,
                       float dropout_p, unsigned long long seed, unsigned site, void* dh1, float* dfilm, int dfilm_stride,
                       bsi_stream_t stream);
+/* The same with the activation `act` (BSI_ACT_*) in place of SiLU (residual_block.py:45 with actfn_from_str's ActFn);
+ * bsi_film_silu(_bwd) are these with BSI_ACT_SILU. */
+int bsi_film_act(const void* h1, int M, int N, int HW, const float* film, int film_rows, int film_stride, int act, float dropout_p,
+                 unsigned long long seed, unsigned site, void* y, bsi_stream_t stream);
+int bsi_film_act_bwd(const void* dy, const void* h1, int M, int N, int HW, const float* film, int film_rows, int film_stride, int act,
+                     float dropout_p, unsigned long long seed, unsigned site, void* dh1, float* dfilm, int dfilm_stride,
+                     bsi_stream_t stream);
 /* Backward of bsi_unet_decode: dh fp32 [B*HW, C] is written; dw [Cout, C] and db [Cout] are ACCUMULATED. */
 int bsi_unet_decode_bwd(const float* g_xhat, const float* c_out, int coef_stride, const float* h, int B, int HW, int C,
                         const float* w, int Cout, float* dh, float* dw, float* db, bsi_stream_t stream);
@@ -547,6 +567,9 @@ typedef struct bsi_unet_weights {
     const float *agn_w, *agn_b;                /* center_block.1.fn.0 */
     const void* aqkv_w; const float* aqkv_b;   /* center_block.1.fn.1.to_qkv: bf16 [3*dim][9*dim] */
     const void* aout_w; const float* aout_b;   /* center_block.1.fn.1.to_out: bf16 [dim][9*dim] */
+    int actfn;  /* the model's ActFn (vdm_unet.py:45,65-69; residual_block.py:41-47): BSI_ACT_SILU .. BSI_ACT_TANH, 0 also means SiLU.
+                 * Applied after pos_map.1 and .3, after every residual block's GroupNorm (layers.1) and FiLM (layers.4); not in
+                 * attention or its GroupNorm.  Workspace and tape sizes do not depend on it. */
 } bsi_unet_weights;
 int bsi_unet_cin_pad(const bsi_unet_config* cfg);
 size_t bsi_unet_workspace_bytes(const bsi_unet_config* cfg, int B);
