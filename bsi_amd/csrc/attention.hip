@@ -20,17 +20,33 @@ __device__ __forceinline__ int k_chunk_swz(int row, int chunk) {  // 16-B chunk 
     // 64-B rows (DH 32): four rows share a 256-B bank window; rows r, r+4, r+8, r+12 land in one 64-B quarter, so their chunk keys
     // 0, 3, 2, 1 (= -(r >> 2) & 3) keep each 16-lane group of the row reads (ds_read_b128: 8 rows x chunk g, 8 rows x chunk g ^ 1)
     // on 16 distinct 16-B slots
-    if constexpr (DH == 32) return chunk ^ (-(row >> 2) & 3);
+    // 32-B rows (DH 16): the row reads are 8 bytes per lane, so the swizzle works on the four 8-B slots of a row, see k16_slot below;
+    // this is its upper bit (the staging store swaps the halves of the 16-B chunk for the lower one)
+    if constexpr (DH == 16) return chunk ^ ((row >> 3) & 1);
+    else if constexpr (DH == 32) return chunk ^ (-(row >> 2) & 3);
     else if constexpr (DH == 64) return chunk ^ ((row >> 1) & 7);
     else return chunk ^ (row & 15);
 }
 template <int DH>
 __device__ __forceinline__ int v_block_swz(int row, int blk) {  // 32-B block index within a V row
     // DH 32: a half-wave of the transposed reads touches rows 4g + q' (8 rows) x one 32-B block; rows r and r + 4 share a 64-B quarter
-    if constexpr (DH == 32) return blk ^ ((row >> 2) & 1);
+    // DH 16: a row is one 32-B block, so there is nothing to permute: a half-wave of the transposed reads (g 0, 1 or g 2, 3) covers
+    // rows 4g + q' = 8 whole consecutive rows = 256 contiguous bytes, every bank once
+    if constexpr (DH == 16) return blk;
+    else if constexpr (DH == 32) return blk ^ ((row >> 2) & 1);
     else if constexpr (DH == 64) return blk ^ ((row >> 1) & 3);
     else return blk ^ (row & 7);
 }
+
+// DH 16 K rows (32 B, eight rows per 256-B bank window): lane group g reads the 8 bytes 8g .. 8g+7 of row c16 of a 16-key tile.
+// The 8-B slot g of row r is stored at slot g ^ ((r >> 2) & 3).  The compiler emits these reads either as ds_read_b64 (served as
+// lanes 0-31 and 32-63 against 64 banks) or, two key tiles at a time, as ds_read2st64_b64 (served per 16 lanes against 32 banks):
+//  - 16 lanes of one g, rows 0 .. 15: bank pair (4r + (g ^ (r >> 2))) mod 16 = 4 (r & 3) + (g ^ (r >> 2)), and r & 3, r >> 2 run over
+//    0 .. 3 independently: 16 distinct pairs = all 32 banks once;
+//  - 32 lanes of g 0, 1 (or 2, 3): rows r and r + 8 start on one bank and their keys differ in bit 1, so rows 0 .. 7 take slots
+//    {0, 1} (or {2, 3}) of their row and rows 8 .. 15 the other two: 32 distinct pairs = all 64 banks once.
+__device__ __forceinline__ int k16_slot(int row, int g) { return g ^ ((row >> 2) & 3); }
+__device__ __forceinline__ u32x4 k16_stage(u32x4 v, int row) { return (row & 4) ? u32x4{v[2], v[3], v[0], v[1]} : v; }
 
 // max / sum over the four 16-lane groups of a wave (lanes c, c+16, c+32, c+48) without LDS: the gfx950 lane-group swaps
 // (v_permlane16_swap: odd groups of a <-> even groups of b; v_permlane32_swap: upper half of a <-> lower half of b) applied
@@ -60,7 +76,7 @@ __global__ __launch_bounds__(512) void attention_fwd_kernel(const __bf16* __rest
                                                             int heads, __bf16* __restrict__ out, int ld_out,
                                                             float scale_log2e, float* __restrict__ lse, DropCfg dc) {
     constexpr int RB = DH * 2;        // bytes per K/V row
-    constexpr int KS = DH / 32;       // k-steps of the QK^T contraction
+    constexpr int KS = DH / 32;       // k-steps of the QK^T contraction (DH 16: none of these, one 16x16x16 product per score tile)
     constexpr int KT = KC / 16;       // 16-key tiles per chunk
     constexpr int DT = DH / 16;       // 16-wide d tiles of the output
     constexpr int CPR = DH / 8;       // 16-B chunks per row
@@ -80,8 +96,18 @@ __global__ __launch_bounds__(512) void attention_fwd_kernel(const __bf16* __rest
     const __bf16* Vg = base + 2 * heads * DH;
 
     // Q fragments (B operand): lane holds Q[q0 + 16jq + c16][32ks + 8g .. +7]
-    bf16x8 qf[2][KS];
-    if (active) {
+    bf16x8 qf[2][KS ? KS : 1];
+    // DH 16: the 16x16x16 product takes 4 bf16 per lane, lane group g holds elements 4g .. 4g+3 of its Q (and K) row; its
+    // accumulator layout is that of the 16x16x32 form, so everything after the score tile is shared.  (Zero-extending Q and K to the
+    // 16x16x32 form would double the K reads and the MFMA passes for nothing.)
+    s16x4 qh[2] = {};
+    if constexpr (DH == 16) {
+        if (active) {
+#pragma unroll
+            for (int jq = 0; jq < 2; ++jq)
+                qh[jq] = *reinterpret_cast<const s16x4*>(Qg + (size_t)(q0 + 16 * jq + c16) * ld_qkv + 4 * g);
+        }
+    } else if (active) {
 #pragma unroll
         for (int jq = 0; jq < 2; ++jq)
 #pragma unroll
@@ -108,7 +134,8 @@ __global__ __launch_bounds__(512) void attention_fwd_kernel(const __bf16* __rest
         Vl = lds + tokens * RB;
         for (int idx = tid; idx < ((ABL & 16) ? 0 : tokens * CPR); idx += 512) {
             const int r = idx / CPR, c = idx % CPR;
-            const u32x4 kv = *reinterpret_cast<const u32x4*>(Kg + (size_t)r * ld_qkv + c * 8);
+            u32x4 kv = *reinterpret_cast<const u32x4*>(Kg + (size_t)r * ld_qkv + c * 8);
+            if constexpr (DH == 16) kv = k16_stage(kv, r);
             const u32x4 vv = *reinterpret_cast<const u32x4*>(Vg + (size_t)r * ld_qkv + c * 8);
             *reinterpret_cast<u32x4*>(Kl + r * RB + k_chunk_swz<DH>(r, c) * 16) = kv;
             *reinterpret_cast<u32x4*>(Vl + r * RB + (v_block_swz<DH>(r, c >> 1) * 2 + (c & 1)) * 16) = vv;
@@ -121,7 +148,8 @@ __global__ __launch_bounds__(512) void attention_fwd_kernel(const __bf16* __rest
             // ---- stage K and V chunk: KC rows x CPR chunks each, 512 threads ---------------------------
             for (int idx = tid; idx < KC * CPR; idx += 512) {
                 const int r = idx / CPR, c = idx % CPR;
-                const u32x4 kv = *reinterpret_cast<const u32x4*>(Kg + (size_t)(kc0 + r) * ld_qkv + c * 8);
+                u32x4 kv = *reinterpret_cast<const u32x4*>(Kg + (size_t)(kc0 + r) * ld_qkv + c * 8);
+                if constexpr (DH == 16) kv = k16_stage(kv, r);
                 const u32x4 vv = *reinterpret_cast<const u32x4*>(Vg + (size_t)(kc0 + r) * ld_qkv + c * 8);
                 *reinterpret_cast<u32x4*>(Kl + r * RB + k_chunk_swz<DH>(r, c) * 16) = kv;
                 *reinterpret_cast<u32x4*>(Vl + r * RB + (v_block_swz<DH>(r, c >> 1) * 2 + (c & 1)) * 16) = vv;
@@ -139,6 +167,11 @@ __global__ __launch_bounds__(512) void attention_fwd_kernel(const __bf16* __rest
             s[kt][0] = f32x4{0.f, 0.f, 0.f, 0.f};
             s[kt][1] = f32x4{0.f, 0.f, 0.f, 0.f};
             const int row = 16 * kt + c16;
+            if constexpr (DH == 16) {
+                const s16x4 kh = *reinterpret_cast<const s16x4*>(Kc + row * RB + k16_slot(row, g) * 8);
+                s[kt][0] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(kh, qh[0], s[kt][0], 0, 0, 0);
+                s[kt][1] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(kh, qh[1], s[kt][1], 0, 0, 0);
+            }
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks) {
                 if constexpr (ABL & 8) {
@@ -292,7 +325,7 @@ int launch_attn(const __bf16* qkv, int ld_qkv, int B, int tokens, int heads, __b
                 DropCfg dc, hipStream_t s) {
     const size_t lds = 2 * (size_t)(ALL ? tokens : KC) * DH * 2;
     auto kern = attention_fwd_kernel<DH, KC, false, ALL>;
-    auto kern_d = attention_fwd_kernel<DH, KC, true, ALL>;
+    auto kern_d = attention_fwd_kernel<DH, KC, DH != 16, ALL>;  // no dropout instance at head dim 16 (refused by the caller)
     const int max_lds = ALL ? 2 * 256 * DH * 2 : (int)lds;
     set_max_lds(reinterpret_cast<const void*>(kern), max_lds);
     set_max_lds(reinterpret_cast<const void*>(kern_d), max_lds);
@@ -320,7 +353,7 @@ bool bsi_attention_uses_mask_words(int tokens, int dh) {
 static int attention_fwd_impl(const void* qkv, int ld_qkv, int B, int tokens, int heads, int dh, void* out, int ld_out,
                               float* lse, DropCfg dc, bsi_stream_t stream, void* maskw = nullptr, bool mask_ready = false) {
     BSI_CHECK_ARG(qkv && out && B > 0 && heads > 0, "bsi_attention_fwd: bad args");
-    BSI_CHECK_ARG(dh == 32 || dh == 64 || dh == 128, "bsi_attention_fwd: head dim %d unsupported (32, 64 or 128)", dh);
+    BSI_CHECK_ARG(dh == 16 || dh == 32 || dh == 64 || dh == 128, "bsi_attention_fwd: head dim %d unsupported (16, 32, 64 or 128)", dh);
     BSI_CHECK_ARG(tokens > 0 && tokens % 64 == 0, "bsi_attention_fwd: tokens=%d must be a multiple of 64", tokens);
     BSI_CHECK_ARG(ld_qkv % 8 == 0 && ld_qkv >= 3 * heads * dh && ld_out % 8 == 0 && ld_out >= heads * dh,
                   "bsi_attention_fwd: bad leading dimensions");
@@ -347,6 +380,13 @@ static int attention_fwd_impl(const void* qkv, int ld_qkv, int B, int tokens, in
         if (tokens % 128 == 0) return launch_attn<32, 128>(q, ld_qkv, B, tokens, heads, o, ld_out, lse, dc, s);
         return launch_attn<32, 64>(q, ld_qkv, B, tokens, heads, o, ld_out, lse, dc, s);
     }
+    if (dh == 16) {
+        // the VDM-UNet's centre attention with 8 heads at dim 128 (or 4 at dim 64): one 16x16x16 MFMA per score tile, one output
+        // d-tile; dispatch as for head dim 32 (resident K and V: 16 KB at 256 tokens)
+        if (tokens <= 256) return launch_attn<16, 64, true>(q, ld_qkv, B, tokens, heads, o, ld_out, lse, dc, s);
+        if (tokens % 128 == 0) return launch_attn<16, 128>(q, ld_qkv, B, tokens, heads, o, ld_out, lse, dc, s);
+        return launch_attn<16, 64>(q, ld_qkv, B, tokens, heads, o, ld_out, lse, dc, s);
+    }
     if (tokens % 128 == 0) return launch_attn<128, 128>(q, ld_qkv, B, tokens, heads, o, ld_out, lse, dc, s);
     return launch_attn<128, 64>(q, ld_qkv, B, tokens, heads, o, ld_out, lse, dc, s);
 }
@@ -364,6 +404,8 @@ extern "C" int bsi_attention_fwd_lse(const void* qkv, int ld_qkv, int B, int tok
 
 int bsi_attention_fwd_train(const void* qkv, int ld_qkv, int B, int tokens, int heads, int dh, void* out, int ld_out,
                             float* lse, DropCfg dc, bsi_stream_t stream, void* maskw, bool mask_ready) {
+    // the training entries (attention dropout, mask words) serve the DiT; head dim 16 has no dropout instance
+    BSI_CHECK_ARG(dh != 16, "bsi_attention_fwd_train: head dim 16 unsupported (32, 64 or 128); use bsi_attention_fwd_lse");
     return attention_fwd_impl(qkv, ld_qkv, B, tokens, heads, dh, out, ld_out, lse, dc, stream,
                               bsi_attention_uses_mask_words(tokens, dh) ? maskw : nullptr, mask_ready);
 }

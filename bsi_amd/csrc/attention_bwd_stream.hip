@@ -19,7 +19,10 @@ __device__ __forceinline__ int swz(int r) {
     // 64-B rows (DH 32): rows r, r+4, r+8, r+12 share a 64-B quarter of the 256-B bank window; keys 0, 3, 2, 1 make the row reads
     // (16-lane groups: 8 rows x chunk g, 8 rows x chunk g ^ 1) and the transposed reads (half-wave: rows 4g + q', chunk pair 2dt,
     // 2dt + 1 -- the keys of r and r + 4 differ in bit 1) conflict-free
-    if constexpr (DH == 32) return -(r >> 2) & 3;
+    // 32-B rows (DH 16): the swizzle works on the four 8-B slots of a row (slot16 below); this is its upper bit, the store of a
+    // 16-B chunk swaps its halves for the lower one
+    if constexpr (DH == 16) return (r >> 3) & 1;
+    else if constexpr (DH == 32) return -(r >> 2) & 3;
     else if constexpr (DH == 64) return ((r >> 1) & 3) << 1;
     else return (r & 7) << 1;
 }
@@ -27,6 +30,24 @@ template <int DH>
 __device__ __forceinline__ const char* rc(const char* tile, int r, int c) {
     return tile + r * (DH * 2) + ((c ^ swz<DH>(r)) << 4);
 }
+
+// DH 16 (32-B rows, eight per 256-B bank window): the 8-B slot p of row r is stored at slot p ^ ((r >> 2) & 3).
+//  - Row reads (lane group g: slot g of row c16) come out as ds_read_b64 (lanes 0-31, 32-63 against 64 banks) or, two tiles at a
+//    time, as ds_read2st64_b64 (per 16 lanes against 32 banks).  16 lanes of one g: bank pair 4 (r & 3) + (g ^ (r >> 2)), r & 3 and
+//    r >> 2 independent: all 32 banks once.  32 lanes of g 0, 1 (2, 3): rows r and r + 8 share their first bank and their keys differ in
+//    bit 1, so they take slots {0, 1} and {2, 3} of their rows: all 64 banks once.
+//  - Transposed reads (lane 4q' + p of group g: slot p of row 4g + q'): a half-wave covers 8 consecutive rows whole, 256 contiguous
+//    bytes whatever the in-row permutation.
+__device__ __forceinline__ const char* slot16(const char* tile, int r, int p) { return tile + r * 32 + ((p ^ ((r >> 2) & 3)) << 3); }
+__device__ __forceinline__ s16x4 row4(const char* tile, int r, int g) { return *reinterpret_cast<const s16x4*>(slot16(tile, r, g)); }
+__device__ __forceinline__ u32x4 stage16(u32x4 v, int r) { return (r & 4) ? u32x4{v[2], v[3], v[0], v[1]} : v; }
+// address a lane hands to the transposed read of d-tile dt: columns 16dt + 4p .. +3 of `row`
+template <int DH>
+__device__ __forceinline__ const char* trp(const char* tile, int row, int dt, int p) {
+    if constexpr (DH == 16) return slot16(tile, row, p);
+    else return rc<DH>(tile, row, 2 * dt + (p >> 1)) + 8 * (p & 1);
+}
+__device__ __forceinline__ s16x4 grow4(const __bf16* p, int g) { return *reinterpret_cast<const s16x4*>(p + 4 * g); }
 
 #define TR(ptr) __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(ptr))
 
@@ -37,7 +58,10 @@ __global__ __launch_bounds__(512) void attention_bwd_stream_kernel(const __bf16*
                                                                    __bf16* __restrict__ dqkv, int ld_dqkv, float scale) {
     constexpr int RB = DH * 2, CPR = DH / 8, KS = DH / 32, DT = DH / 16;
     constexpr int JR = DH <= 64 ? 2 : 1;      // 16-row tiles owned by a wave
-    constexpr int LPT = 2 * 64 * CPR / 512;   // 16-B loads per thread per streamed chunk (two tiles)
+    constexpr int NLD = 2 * 64 * CPR;         // 16-B loads per streamed chunk (two tiles)
+    constexpr int LPT = NLD < 512 ? 1 : NLD / 512;  // per thread; DH 16: 256 loads, the threads of waves 0 .. 3 take one each
+    constexpr int KS1 = KS ? KS : 1;          // DH 16 has no 32-wide k-step: one 16x16x16 product per tile, 4 bf16 per lane (group g:
+                                              // elements 4g .. 4g+3), accumulators laid out as those of the 16x16x32 form
     extern __shared__ __attribute__((aligned(16))) char lds[];
     char* TA = lds;
     char* TB = TA + 64 * RB;
@@ -78,6 +102,7 @@ __global__ __launch_bounds__(512) void attention_bwd_stream_kernel(const __bf16*
 
     u32x4 pre[LPT];
     auto prefetch = [&](const __bf16* A, int lda, const __bf16* Bp, int ldb, int row0) {
+        if constexpr (NLD < 512) { if (tid >= NLD) return; }
 #pragma unroll
         for (int i = 0; i < LPT; ++i) {
             const int idx = tid + i * 512;
@@ -88,11 +113,13 @@ __global__ __launch_bounds__(512) void attention_bwd_stream_kernel(const __bf16*
         }
     };
     auto commit = [&]() {
+        if constexpr (NLD < 512) { if (tid >= NLD) return; }
 #pragma unroll
         for (int i = 0; i < LPT; ++i) {
             const int idx = tid + i * 512;
             const int tile = idx / (64 * CPR), rem = idx % (64 * CPR);
             const int r = rem / CPR, c = rem % CPR;
+            if constexpr (DH == 16) pre[i] = stage16(pre[i], r);
             *reinterpret_cast<u32x4*>((tile == 0 ? TA : TB) + r * RB + ((c ^ swz<DH>(r)) << 4)) = pre[i];
         }
     };
@@ -104,11 +131,16 @@ __global__ __launch_bounds__(512) void attention_bwd_stream_kernel(const __bf16*
 
     // =========================== pass 1: dQ ===========================
     {
-        bf16x8 qf[JR][KS], dof[JR][KS];
+        bf16x8 qf[JR][KS1], dof[JR][KS1];
+        s16x4 qh[JR] = {}, doh[JR] = {};
         float lq[JR], dq_delta[JR];
 #pragma unroll
         for (int jq = 0; jq < JR; ++jq) {
             const int q = r0c + 16 * jq + c16;
+            if constexpr (DH == 16) {
+                qh[jq] = grow4(Qg + (size_t)q * ld_qkv, g);
+                doh[jq] = grow4(Dg + (size_t)q * ld_o, g);
+            }
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks) {
                 qf[jq][ks] = *reinterpret_cast<const bf16x8*>(Qg + (size_t)q * ld_qkv + 32 * ks + 8 * g);
@@ -136,6 +168,14 @@ __global__ __launch_bounds__(512) void attention_bwd_stream_kernel(const __bf16*
 #pragma unroll
                 for (int jq = 0; jq < JR; ++jq) s[kt][jq] = dp[kt][jq] = f32x4{0.f, 0.f, 0.f, 0.f};
                 const int row = 16 * kt + c16;
+                if constexpr (DH == 16) {
+                    const s16x4 kh = row4(TA, row, g), vh = row4(TB, row, g);
+#pragma unroll
+                    for (int jq = 0; jq < JR; ++jq) {
+                        s[kt][jq] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(kh, qh[jq], s[kt][jq], 0, 0, 0);
+                        dp[kt][jq] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(vh, doh[jq], dp[kt][jq], 0, 0, 0);
+                    }
+                }
 #pragma unroll
                 for (int ks = 0; ks < KS; ++ks) {
                     const bf16x8 kf = *reinterpret_cast<const bf16x8*>(rc<DH>(TA, row, 4 * ks + g));
@@ -170,8 +210,8 @@ __global__ __launch_bounds__(512) void attention_bwd_stream_kernel(const __bf16*
 #pragma unroll
                 for (int dt = 0; dt < DT; ++dt) {
                     Frag kt_;
-                    kt_.h[0] = TR(rc<DH>(TA, rowA, 2 * dt + (pp >> 1)) + 8 * (pp & 1));
-                    kt_.h[1] = TR(rc<DH>(TA, rowB, 2 * dt + (pp >> 1)) + 8 * (pp & 1));
+                    kt_.h[0] = TR(trp<DH>(TA, rowA, dt, pp));
+                    kt_.h[1] = TR(trp<DH>(TA, rowB, dt, pp));
 #pragma unroll
                     for (int jq = 0; jq < JR; ++jq)
                         dq[dt][jq] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kt_.v, dsf[jq], dq[dt][jq], 0, 0, 0);
@@ -195,10 +235,15 @@ __global__ __launch_bounds__(512) void attention_bwd_stream_kernel(const __bf16*
 
     // =========================== pass 2: dK, dV ===========================
     {
-        bf16x8 kf[JR][KS], vf[JR][KS];
+        bf16x8 kf[JR][KS1], vf[JR][KS1];
+        s16x4 kh[JR] = {}, vh[JR] = {};
 #pragma unroll
         for (int jk = 0; jk < JR; ++jk) {
             const int k = r0c + 16 * jk + c16;
+            if constexpr (DH == 16) {
+                kh[jk] = grow4(Kg + (size_t)k * ld_qkv, g);
+                vh[jk] = grow4(Vg + (size_t)k * ld_qkv, g);
+            }
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks) {
                 kf[jk][ks] = *reinterpret_cast<const bf16x8*>(Kg + (size_t)k * ld_qkv + 32 * ks + 8 * g);
@@ -222,6 +267,14 @@ __global__ __launch_bounds__(512) void attention_bwd_stream_kernel(const __bf16*
 #pragma unroll
                 for (int jk = 0; jk < JR; ++jk) s[qt][jk] = dp[qt][jk] = f32x4{0.f, 0.f, 0.f, 0.f};
                 const int row = 16 * qt + c16;
+                if constexpr (DH == 16) {
+                    const s16x4 qa = row4(TA, row, g), da = row4(TB, row, g);
+#pragma unroll
+                    for (int jk = 0; jk < JR; ++jk) {
+                        s[qt][jk] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(qa, kh[jk], s[qt][jk], 0, 0, 0);
+                        dp[qt][jk] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(da, vh[jk], dp[qt][jk], 0, 0, 0);
+                    }
+                }
 #pragma unroll
                 for (int ks = 0; ks < KS; ++ks) {
                     const bf16x8 qa = *reinterpret_cast<const bf16x8*>(rc<DH>(TA, row, 4 * ks + g));
@@ -263,10 +316,10 @@ __global__ __launch_bounds__(512) void attention_bwd_stream_kernel(const __bf16*
 #pragma unroll
                 for (int dt = 0; dt < DT; ++dt) {
                     Frag dot, qt_;
-                    dot.h[0] = TR(rc<DH>(TB, rowA, 2 * dt + (pp >> 1)) + 8 * (pp & 1));
-                    dot.h[1] = TR(rc<DH>(TB, rowB, 2 * dt + (pp >> 1)) + 8 * (pp & 1));
-                    qt_.h[0] = TR(rc<DH>(TA, rowA, 2 * dt + (pp >> 1)) + 8 * (pp & 1));
-                    qt_.h[1] = TR(rc<DH>(TA, rowB, 2 * dt + (pp >> 1)) + 8 * (pp & 1));
+                    dot.h[0] = TR(trp<DH>(TB, rowA, dt, pp));
+                    dot.h[1] = TR(trp<DH>(TB, rowB, dt, pp));
+                    qt_.h[0] = TR(trp<DH>(TA, rowA, dt, pp));
+                    qt_.h[1] = TR(trp<DH>(TA, rowB, dt, pp));
 #pragma unroll
                     for (int jk = 0; jk < JR; ++jk) {
                         dv[dt][jk] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(dot.v, pf[jk], dv[dt][jk], 0, 0, 0);
@@ -314,7 +367,7 @@ int launch_stream(const __bf16* qkv, int ld_qkv, const __bf16* o, const __bf16* 
 extern "C" int bsi_attention_bwd_long(const void* qkv, int ld_qkv, const void* out, const void* dout, int ld_o, const float* lse,
                                       int B, int tokens, int heads, int dh, void* dqkv, int ld_dqkv, bsi_stream_t stream) {
     BSI_CHECK_ARG(qkv && out && dout && lse && dqkv && B > 0 && heads > 0, "bsi_attention_bwd_long: bad args");
-    BSI_CHECK_ARG(dh == 32 || dh == 64 || dh == 128, "bsi_attention_bwd_long: head dim %d unsupported (32, 64 or 128)", dh);
+    BSI_CHECK_ARG(dh == 16 || dh == 32 || dh == 64 || dh == 128, "bsi_attention_bwd_long: head dim %d unsupported (16, 32, 64 or 128)", dh);
     BSI_CHECK_ARG(tokens > 0 && tokens % 64 == 0 && tokens <= 8192, "bsi_attention_bwd_long: tokens=%d must be a multiple of 64, <= 8192",
                   tokens);
     BSI_CHECK_ARG(ld_qkv % 8 == 0 && ld_o % 8 == 0 && ld_dqkv % 4 == 0, "bsi_attention_bwd_long: bad leading dimensions");
@@ -323,6 +376,7 @@ extern "C" int bsi_attention_bwd_long(const void* qkv, int ld_qkv, const void* o
     const __bf16* o = reinterpret_cast<const __bf16*>(out);
     const __bf16* d = reinterpret_cast<const __bf16*>(dout);
     __bf16* dq = reinterpret_cast<__bf16*>(dqkv);
+    if (dh == 16) return launch_stream<16>(q, ld_qkv, o, d, ld_o, lse, B, tokens, heads, dq, ld_dqkv, s);
     if (dh == 32) return launch_stream<32>(q, ld_qkv, o, d, ld_o, lse, B, tokens, heads, dq, ld_dqkv, s);
     if (dh == 64) return launch_stream<64>(q, ld_qkv, o, d, ld_o, lse, B, tokens, heads, dq, ld_dqkv, s);
     return launch_stream<128>(q, ld_qkv, o, d, ld_o, lse, B, tokens, heads, dq, ld_dqkv, s);

@@ -176,7 +176,7 @@ extern "C" int bsi_unet_forward(const bsi_unet_config* cfg, const bsi_unet_weigh
                   "bsi_unet_forward: c_in/c_skip/c_out must be given together");
     const UDims d = udims(cfg, B);
     const int dim = cfg->dim, H = cfg->H, W = cfg->W, L = cfg->levels;
-    BSI_CHECK_ARG(dim % 32 == 0 && (dim == 64 || dim == 128) && dim % cfg->heads == 0 && (d.dh == 64 || d.dh == 128) && d.HW % 64 == 0,
+    BSI_CHECK_ARG(dim % 32 == 0 && (dim == 64 || dim == 128) && dim % cfg->heads == 0 && (d.dh == 16 || d.dh == 32 || d.dh == 64 || d.dh == 128) && d.HW % 64 == 0,
                   "bsi_unet_forward: unsupported geometry dim=%d heads=%d HW=%d", dim, cfg->heads, d.HW);
     const int act = unet_actfn(w);  // residual_block.py:41-47: after layers.0 (GroupNorm) and the FiLM stage
     BSI_CHECK_ARG(act > 0, "bsi_unet_forward: unknown activation code %d", w->actfn);

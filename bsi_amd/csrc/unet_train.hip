@@ -229,7 +229,7 @@ int gemm(const void* A, int lda, const void* W, int ldw, const float* bias, void
 }
 
 int check_geometry(const bsi_unet_config* cfg, const UD& d, const char* who) {
-    BSI_CHECK_ARG((cfg->dim == 64 || cfg->dim == 128) && cfg->dim % cfg->heads == 0 && (d.dh == 64 || d.dh == 128) && d.HW % 64 == 0 &&
+    BSI_CHECK_ARG((cfg->dim == 64 || cfg->dim == 128) && cfg->dim % cfg->heads == 0 && (d.dh == 16 || d.dh == 32 || d.dh == 64 || d.dh == 128) && d.HW % 64 == 0 &&
                       cfg->emb_size <= 64 && cfg->emb_size % 2 == 0 && cfg->c_dim % 64 == 0,
                   "%s: unsupported geometry dim=%d heads=%d HW=%d emb=%d c_dim=%d", who, cfg->dim, cfg->heads, d.HW, cfg->emb_size,
                   cfg->c_dim);

@@ -392,7 +392,15 @@ class DPTrainer:
         self.seg_tab = self._seg_table(self.seg_rows, dev) if dev.type == "cuda" else None
 
     def _setup_exchange_state(self, dev, depth):
-        self.comm_stream = torch.cuda.Stream(device=dev) if (self.exchange or (self.overlap_gather and dev.type == "cuda")) else None
+        # The overlapped gather runs on a stream of HIGH priority, as FSDP's all-gather does: its small copies go ahead of the
+        # forward's kernels, and the stream does not land on the hardware queue of the caller's compute stream.  (HIP deals streams
+        # to GPU_MAX_HW_QUEUES hardware queues, 4 by default, and a queue runs in order: measured on an MI355X with 4 queues, the
+        # first stream of torch's default-priority pool shares its queue with the first of the high-priority pool, and a forward
+        # launched there behind a gather that is still running waits for it -- a whole forward is left after the last bucket
+        # instead of half of one.)  Without overlap_gather the stream is the one it has always been.
+        prio = -1 if self.overlap_gather else 0
+        self.comm_stream = (torch.cuda.Stream(device=dev, priority=prio)
+                            if (self.exchange or (self.overlap_gather and dev.type == "cuda")) else None)
         self.events = None
         if self.exchange and self.bucketed:
             self.events = [torch.cuda.Event() for _ in range(depth)]

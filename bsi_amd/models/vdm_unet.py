@@ -20,7 +20,8 @@ class _Slot(nn.Identity):
 
 
 class Attention2D(nn.Module):
-    """Parameter holder for bsi/nn/attention.py:21-41 (to_qkv / to_out 3x3 convolutions)."""
+    """Parameter holder for bsi/nn/attention.py:21-41 (to_qkv / to_out 3x3 convolutions).  `heads` splits the to_qkv channels
+    '(qkv h c)'; the native attention kernels take head dims 16, 32, 64 and 128."""
 
     def __init__(self, dim: int, *, heads: int = 4, padding_mode: str = "zeros"):
         super().__init__()
@@ -65,7 +66,12 @@ class SimplifiedUNet(nn.Module):
 
 
 class DenoisingVDMUNet(nn.Module):
-    """U-Net as in the VDM paper without down-sampling — same constructor as bsi.models.vdm_unet.DenoisingVDMUNet."""
+    """U-Net as in the VDM paper without down-sampling — same constructor as bsi.models.vdm_unet.DenoisingVDMUNet.
+
+    `n_attention_heads` (the centre Attention2D) runs natively for every count whose head dim `dim // n_attention_heads` is 16, 32, 64
+    or 128 (dim 128: 1, 2, 4, 8 heads; dim 64: 1, 2, 4).  As in the reference the constructor accepts any count; another head dim fails
+    at the first forward / sample / elbo / train_loss with the engine's `unsupported geometry` message.  The state dict does not
+    depend on the head count."""
 
     def __init__(self, data_shape, pos_emb: NyquistPositionalEmbedding, actfn: str, dim: int, levels: int,
                  pos_emb_mult: int, n_attention_heads: int = 1, dropout: float | None = None,
@@ -82,8 +88,8 @@ class DenoisingVDMUNet(nn.Module):
                                       "configuration)")
         if downsampling_attention and dim != 128:
             raise NotImplementedError(f"bsi_amd.DenoisingVDMUNet: downsampling_attention=True needs dim=128 (the per-block "
-                                      f"Attention2D has 4 heads; dim={dim} gives head dim {dim // 4}, and the native attention "
-                                      "kernels implement head dims 32, 64 and 128)")
+                                      f"Attention2D has 4 heads; dim={dim} gives head dim {dim // 4}, and the engines run the per-block "
+                                      "attention at head dim 32 only)")
         n_channels = data_shape[0]
         in_features = out_features = n_channels
         if fourier_features is not None:

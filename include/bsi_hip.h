@@ -297,7 +297,8 @@ int bsi_resid2_ln_modulate(float* x, int M, int d, float eps, const void* delta0
 
 /* dit.py:39-46 / attention.py:34-40: softmax(q k^T / sqrt(dh)) v per (batch, head), non-causal.
  * qkv: bf16 [B, tokens, 3, heads, dh] (row stride ld_qkv elements); out: bf16 [B, tokens, heads*dh]
- * (row stride ld_out).  dh in {32, 64, 128} (32: the VDM-UNet's per-block Attention2D, 4 heads at dim 128); tokens % 64 == 0. */
+ * (row stride ld_out).  dh in {16, 32, 64, 128} (32: the VDM-UNet's per-block Attention2D, 4 heads at dim 128; 16: its centre
+ * Attention2D with 8 heads at dim 128 or 4 at dim 64); tokens % 64 == 0. */
 int bsi_attention_fwd(const void* qkv, int ld_qkv, int B, int tokens, int heads, int dh, void* out, int ld_out,
                       bsi_stream_t stream);
 
@@ -309,8 +310,8 @@ int bsi_attention_fwd_lse(const void* qkv, int ld_qkv, int B, int tokens, int he
 int bsi_attention_bwd(const void* qkv, int ld_qkv, const void* out, const void* dout, int ld_o, const float* lse,
                       int B, int tokens, int heads, int dh, void* dqkv, int ld_dqkv, bsi_stream_t stream);
 /* Same contract for long sequences / wide heads (UNet centre attention, attention.py:18,38: 1024 positions, dh 128):
- * the other side of each pass is streamed through LDS; tokens % 64 == 0, dh 32, 64 or 128 (32: the per-block attention of
- * residual_block.py:50-64), no dropout. */
+ * the other side of each pass is streamed through LDS; tokens % 64 == 0, dh 16, 32, 64 or 128 (32: the per-block attention of
+ * residual_block.py:50-64; 16 and 32: the centre attention with n_attention_heads 8 and 4 at dim 128), no dropout. */
 int bsi_attention_bwd_long(const void* qkv, int ld_qkv, const void* out, const void* dout, int ld_o, const float* lse,
                            int B, int tokens, int heads, int dh, void* dqkv, int ld_dqkv, bsi_stream_t stream);
 
@@ -540,7 +541,7 @@ int bsi_unet_decode(const float* h, int B, int HW, int C, const float* w, const 
  * [ResBlock, Residual(GroupNorm -> Attention2D), ResBlock], levels blocks up on cat(x, skip)). */
 typedef struct bsi_unet_config {
     int C, H, W;      /* data_shape */
-    int dim, levels, heads;
+    int dim, levels, heads;   /* dim 64 or 128; heads = n_attention_heads of the centre Attention2D: dim / heads in {16, 32, 64, 128} */
     int ff_nmin, ff_nmax;
     int emb_size;     /* pos_emb.size (32) */
     int c_dim;        /* pos_emb.size * pos_emb_mult (128) */
@@ -679,7 +680,8 @@ int bsi_attention_dropout_words(float p, unsigned long long seed, unsigned site,
 /* dit.py:43-44 in training: F.scaled_dot_product_attention(q, k, v, dropout_p = p) and its autograd, with the mask above (row =
  * (b * heads + h) * tokens + query, col = key).  words: NULL (both sides evaluate the hash), or -- 256 tokens, head dim 64 only -- a
  * buffer of 8 KB per (image, head) that the forward FILLS with the lane-mask words and the backward READS (what the training engine
- * keeps on its tape); pass the same value to both.  lse as bsi_attention_fwd_lse.  p = 0 is plain attention. */
+ * keeps on its tape); pass the same value to both.  lse as bsi_attention_fwd_lse.  p = 0 is plain attention.  Forward: dh 32, 64 or 128
+ * (head dim 16 is refused: it has no dropout instance); backward: dh 64, tokens <= 256. */
 int bsi_attention_fwd_dropout(const void* qkv, int ld_qkv, int B, int tokens, int heads, int dh, void* out, int ld_out, float* lse,
                               float p, unsigned long long seed, unsigned site, void* words, bsi_stream_t stream);
 int bsi_attention_bwd_dropout(const void* qkv, int ld_qkv, const void* out, const void* dout, int ld_o, const float* lse, int B,

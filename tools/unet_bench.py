@@ -4,6 +4,7 @@
 --downsampling-attention: the same UNet with Residual(GroupNorm -> Attention2D) after every residual block (4 heads of 32
 channels; the GFLOP figure then counts only the default UNet's work).  --train N: also time N train_loss backward steps (B images).
 --actfn NAME: the model's activation (silu, the default, gelu, relu, softplus, tanh).
+--heads N: n_attention_heads of the centre Attention2D (1, the default, 2, 4 or 8: head dims 128 .. 16).
 """
 import argparse
 import os
@@ -20,6 +21,7 @@ from bsi_amd.nn import FourierFeatures  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--downsampling-attention", action="store_true")
+ap.add_argument("--heads", type=int, default=1, metavar="N")
 ap.add_argument("--train", type=int, default=0, metavar="N")
 ap.add_argument("--actfn", default="silu", choices=("silu", "gelu", "relu", "softplus", "tanh"))
 args = ap.parse_args()
@@ -28,7 +30,7 @@ K = int(os.environ.get("K", "128"))
 dev = torch.device("cuda", 0)
 shape = (3, 32, 32)
 torch.manual_seed(0)
-m = DenoisingVDMUNet(shape, NyquistPositionalEmbedding(32, 100), args.actfn, 128, 32, 4, n_attention_heads=1, dropout=0.1,
+m = DenoisingVDMUNet(shape, NyquistPositionalEmbedding(32, 100), args.actfn, 128, 32, 4, n_attention_heads=args.heads, dropout=0.1,
                      downsampling_attention=args.downsampling_attention,
                      fourier_features=FourierFeatures(n_min=6, n_max=8)).to(dev).eval()
 bsi = BSI(m, data_shape=shape, lambda_0=1e-2, alpha_M=1e6, alpha_R=2e6, k=K, preconditioning="edm",
@@ -42,7 +44,8 @@ with torch.no_grad():
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
 assert torch.isfinite(out).all()
-tag = (" downsampling_attention" if args.downsampling_attention else "") + (f" actfn={args.actfn}" if args.actfn != "silu" else "")
+tag = (" downsampling_attention" if args.downsampling_attention else "") + (f" actfn={args.actfn}" if args.actfn != "silu" else "") + (
+    f" heads={args.heads}" if args.heads != 1 else "")
 print(f"UNet{tag} BSI.sample k={K} B={B}: {B / dt:.2f} images/s, {B / dt * (K + 1) * 53.47 / 1e3:.0f} model TFLOP/s")
 if args.train:
     m.train()
