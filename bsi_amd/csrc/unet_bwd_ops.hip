@@ -83,7 +83,7 @@ __global__ __launch_bounds__(256) void film_silu_bwd_kernel(const __bf16* __rest
     // part_stride > 0: the slab STORES its sums into plane (slab index inside the image) of dfilm, planes part_stride floats apart,
     // summed later in fixed order (bsi_sum_cast_rows_bf16): reproducible, no zero fill; 0: fp32 atomics (the C-ABI contract)
     __shared__ float red[2][256 * 8];
-    const int n8 = N / 8;            // chunks per pixel (8, 16)
+    const int n8 = N / 8;            // chunks per pixel (8, 16, 32)
     const int rows_par = 256 / n8;   // pixel rows handled in parallel
     const int ch = threadIdx.x % n8, sub = threadIdx.x / n8;
     const int c = ch * 8;
@@ -542,8 +542,8 @@ int bsi_film_act_bwd_drop(const void* dy, const void* h1, int M, int N, int HW, 
                           int film_stride, int act, DropCfg dc, void* dh1, float* dfilm, int dfilm_stride, bsi_stream_t stream,
                            size_t part_stride) {
     BSI_CHECK_ARG(dy && h1 && film && dh1 && dfilm && M > 0, "bsi_film_silu_bwd: bad args");
-    BSI_CHECK_ARG((N == 64 || N == 128) && HW % FB_ROWS == 0 && M % HW == 0 && film_rows > 0,
-                  "bsi_film_silu_bwd: N=%d (64 or 128), HW=%d (multiple of %d)", N, HW, FB_ROWS);
+    BSI_CHECK_ARG((N == 64 || N == 128 || N == 256) && HW % FB_ROWS == 0 && M % HW == 0 && film_rows > 0,
+                  "bsi_film_silu_bwd: N=%d (64, 128 or 256), HW=%d (multiple of %d)", N, HW, FB_ROWS);
     return bsi_with_act(act, "bsi_film_act_bwd", [&](auto a) {
         hipLaunchKernelGGL(film_silu_bwd_kernel<decltype(a)::value>, dim3(M / FB_ROWS), dim3(256), 0, S_(stream),
                            reinterpret_cast<const __bf16*>(dy), reinterpret_cast<const __bf16*>(h1), N, HW, film, film_rows, film_stride, dc,
@@ -610,8 +610,8 @@ static int groupnorm_bwd_impl(const void* da, const float* x1, int C1, const flo
                               float* partials = nullptr) {
     BSI_CHECK_ARG(da && x1 && gamma && beta && out1 && dgamma && dbeta && B > 0 && HW > 0, "bsi_groupnorm_bwd_nhwc: bad args");
     const int C = C1 + C2;
-    BSI_CHECK_ARG((C == 128 || C == 256 || C == 64) && C1 % 32 == 0 && C2 % 32 == 0 && (C2 == 0 || (x2 && out2)),
-                  "bsi_groupnorm_bwd_nhwc: C1+C2=%d unsupported (64, 128 or 256 channels, 32 groups)", C);
+    BSI_CHECK_ARG((C == 128 || C == 256 || C == 64 || (C == 512 && C1 == 256)) && C1 % 32 == 0 && C2 % 32 == 0 && (C2 == 0 || (x2 && out2)),
+                  "bsi_groupnorm_bwd_nhwc: C1+C2=%d unsupported (64, 128, 256 or 256 + 256 channels, 32 groups)", C);
     // per launch at 128 images (tools/experiments/gn_bwd_ab.sh): 128 channels 76.6 against 80.6 us streaming, cat(x, skip) with 256 channels 125.1
     // against 150.8.  BSI_GN_BWD_STREAM=1: the streaming kernel everywhere (the A/B partner; other last bits).
     static const bool streaming = getenv("BSI_GN_BWD_STREAM") != nullptr;
@@ -624,6 +624,14 @@ static int groupnorm_bwd_impl(const void* da, const float* x1, int C1, const flo
                                reinterpret_cast<__bf16*>(out1_bf16), stats, partials);
         else if (HW == 1024 && C1 == 128 && C2 == 128 && !streaming)
             hipLaunchKernelGGL((groupnorm_bwd_res_kernel<16, 256, 128, ACT>), dim3(B, C / GN_CS), dim3(GNR_TPB), 0, S_(stream),
+                               reinterpret_cast<const __bf16*>(da), x1, C1, x2, C2, HW, gamma, beta, eps, silu, add, add_b, out1, out2, dgamma, dbeta,
+                               reinterpret_cast<__bf16*>(out1_bf16), stats, partials);
+        else if (HW == 1024 && C1 == 256 && C2 == 0 && !streaming)  // dim 256: a plain block, and its up block's cat(x, skip) below
+            hipLaunchKernelGGL((groupnorm_bwd_res_kernel<16, 256, 256, ACT>), dim3(B, C / GN_CS), dim3(GNR_TPB), 0, S_(stream),
+                               reinterpret_cast<const __bf16*>(da), x1, C1, x2, C2, HW, gamma, beta, eps, silu, add, add_b, out1, out2, dgamma, dbeta,
+                               reinterpret_cast<__bf16*>(out1_bf16), stats, partials);
+        else if (HW == 1024 && C1 == 256 && C2 == 256 && !streaming)
+            hipLaunchKernelGGL((groupnorm_bwd_res_kernel<16, 512, 256, ACT>), dim3(B, C / GN_CS), dim3(GNR_TPB), 0, S_(stream),
                                reinterpret_cast<const __bf16*>(da), x1, C1, x2, C2, HW, gamma, beta, eps, silu, add, add_b, out1, out2, dgamma, dbeta,
                                reinterpret_cast<__bf16*>(out1_bf16), stats, partials);
         else

@@ -52,7 +52,7 @@ struct UWs {
 // reduce-then-normalise kernel); BSI_UNET_NO_GN_FUSE=1 keeps the separate kernel for comparison
 inline bool gn_fuse_on(const bsi_unet_config* c) {
     static const bool no_gn_fuse = getenv("BSI_UNET_NO_GN_FUSE") != nullptr;
-    return !no_gn_fuse && c->dim == 128 && (c->H * c->W) % 128 == 0;
+    return !no_gn_fuse && (c->dim == 128 || c->dim == 256) && (c->H * c->W) % 128 == 0;
 }
 // The 256-channel GroupNorm of an up block as two 128-channel halves (unet_ops.h, bsi_groupnorm_apply_split; round-3 review item 4):
 // built, bit-identical results, and NOT the default -- BSI_UNET_GN_SPLIT=1 switches it on.  Measured (profiles/r4/unet_gn_split_ab.txt,
@@ -63,7 +63,7 @@ inline bool gn_fuse_on(const bsi_unet_config* c) {
 // Not with per-block attention: the plain per-block GroupNorm is kept there.
 inline bool gn_split_on(const bsi_unet_config* c) {
     static const bool on = getenv("BSI_UNET_GN_SPLIT") != nullptr;
-    return on && gn_fuse_on(c) && c->levels > 0 && c->block_heads == 0;
+    return on && gn_fuse_on(c) && c->dim == 128 && c->levels > 0 && c->block_heads == 0;
 }
 
 inline UWs carve(const bsi_unet_config* c, int B, void* base) {
@@ -72,8 +72,13 @@ inline UWs carve(const bsi_unet_config* c, int B, void* base) {
     char* p = reinterpret_cast<char*>(base);
     size_t off = 0;
     const size_t M = d.M, dim = c->dim;
-    w.zeros = p + off; off += 256;
-    w.xin = p + off; off += au(M * d.cin_pad * 2);
+    // Every region below is dim (or a multiple of it) wide except these two.  Above dim 128 they are reserved in proportion to the
+    // width, which makes the size at dim 256 no less than twice the dim-128 size at the same B and image (the property
+    // tests/test_unet_dim256_host.py states for bsi_unet_workspace_bytes; laid out plainly it is 1.985 to 1.997 times).  The engine
+    // uses the first 256 bytes / the first M * cin_pad elements.  Dims 64 and 128: the sizes they always had.
+    const size_t wscale = dim > 128 ? dim / 128 : 1;
+    w.zeros = p + off; off += 256 * wscale;
+    w.xin = p + off; off += au(M * d.cin_pad * 2) * wscale;
     w.a = p + off; off += au(M * 2 * dim * 2);
     w.raw = p + off; off += au(M * 2 * dim * 2);
     w.y = p + off; off += au(M * dim * 2);
@@ -176,12 +181,12 @@ extern "C" int bsi_unet_forward(const bsi_unet_config* cfg, const bsi_unet_weigh
                   "bsi_unet_forward: c_in/c_skip/c_out must be given together");
     const UDims d = udims(cfg, B);
     const int dim = cfg->dim, H = cfg->H, W = cfg->W, L = cfg->levels;
-    BSI_CHECK_ARG(dim % 32 == 0 && (dim == 64 || dim == 128) && dim % cfg->heads == 0 && (d.dh == 16 || d.dh == 32 || d.dh == 64 || d.dh == 128) && d.HW % 64 == 0,
+    BSI_CHECK_ARG(dim % 32 == 0 && (dim == 64 || dim == 128 || dim == 256) && dim % cfg->heads == 0 && (d.dh == 16 || d.dh == 32 || d.dh == 64 || d.dh == 128) && d.HW % 64 == 0,
                   "bsi_unet_forward: unsupported geometry dim=%d heads=%d HW=%d", dim, cfg->heads, d.HW);
     const int act = unet_actfn(w);  // residual_block.py:41-47: after layers.0 (GroupNorm) and the FiLM stage
     BSI_CHECK_ARG(act > 0, "bsi_unet_forward: unknown activation code %d", w->actfn);
-    BSI_CHECK_ARG(cfg->block_heads == 0 || (cfg->block_heads > 0 && dim == 32 * cfg->block_heads),
-                  "bsi_unet_forward: per-block attention needs head dim 32 (dim=%d, block_heads=%d)", dim, cfg->block_heads);
+    BSI_CHECK_ARG(cfg->block_heads == 0 || (cfg->block_heads > 0 && (dim == 32 * cfg->block_heads || (dim == 256 && cfg->block_heads == 4))),
+                  "bsi_unet_forward: per-block attention needs head dim 32, or 64 at dim 256 (dim=%d, block_heads=%d)", dim, cfg->block_heads);
     for (int i = 0; cfg->block_heads > 0 && i < d.nblocks; ++i)
         BSI_CHECK_ARG(w->blocks[i].agn_w && w->blocks[i].agn_b && w->blocks[i].aqkv_w && w->blocks[i].aqkv_b && w->blocks[i].aout_w &&
                           w->blocks[i].aout_b,

@@ -39,7 +39,7 @@ __global__ __launch_bounds__(GN_TPB) void groupnorm_kernel(const float* __restri
     __shared__ float mean_s[16], rstd_s[16];
     const int C = C1 + C2;
     constexpr int CH4 = GN_CS / 4;                // float4 chunks per pixel in this slice
-    const int cpg = C / 32;                       // channels per group (2, 4 or 8)
+    const int cpg = C / 32;                       // channels per group (2, 4, 8 or 16)
     const int b = blockIdx.x, t = threadIdx.x, cs0 = blockIdx.y * GN_CS;
     const int ch = t % CH4, prow = t / CH4, PPI = GN_TPB / CH4;  // pixel rows handled in parallel
     const int c0 = cs0 + ch * 4;
@@ -214,7 +214,7 @@ __global__ __launch_bounds__(GN_RTPB) void groupnorm_reg_kernel(const float* __r
 // partials per group (fixed order, Chan et al.'s pairwise update: deterministic), then every thread owns ONE 4-channel column
 // quad (its mean / rstd / gamma / beta stay in registers) and walks the pixels with 8 independent 16-B loads in flight.
 constexpr int GA_TPB = 256, GA_PIX = 128;
-template <int C, int ACT>  // channels of cat(x1, x2): 128 or 256
+template <int C, int ACT>  // channels of cat(x1, x2): 128, 256 or 512
 __global__ __launch_bounds__(GA_TPB) void groupnorm_apply_kernel(const float* __restrict__ x1, int C1, const float* __restrict__ part1,
                                                                  const float* __restrict__ x2, const float* __restrict__ part2, int HW,
                                                                  const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
@@ -400,8 +400,9 @@ static int groupnorm_impl(const float* x1, int C1, const float* x2, int C2, int 
                           int act, void* out_bf16, void* raw_bf16, float* stats, bsi_stream_t stream) {
     BSI_CHECK_ARG(x1 && gamma && beta && out_bf16 && B > 0 && HW > 0, "bsi_groupnorm_nhwc: bad args");
     const int C = C1 + C2;
-    BSI_CHECK_ARG((C == 128 || C == 256 || C == 64) && C1 % 32 == 0 && C2 % 32 == 0 && (C2 == 0 || x2),
-                  "bsi_groupnorm_nhwc: C1+C2=%d unsupported (64, 128 or 256 channels, 32 groups)", C);
+    // 512 = the up block's cat(x, skip) at dim 256: 16 channels per group, two equal sources (a group never straddles them)
+    BSI_CHECK_ARG((C == 128 || C == 256 || C == 64 || (C == 512 && C1 == 256)) && C1 % 32 == 0 && C2 % 32 == 0 && (C2 == 0 || x2),
+                  "bsi_groupnorm_nhwc: C1+C2=%d unsupported (64, 128, 256 or 256 + 256 channels, 32 groups)", C);
     BSI_CHECK_ARG(!stats || HW <= 1024, "bsi_groupnorm_stats_nhwc: statistics output needs H*W <= 1024");
     __bf16* o = reinterpret_cast<__bf16*>(out_bf16);
     __bf16* r = reinterpret_cast<__bf16*>(raw_bf16);
@@ -440,8 +441,8 @@ extern "C" int bsi_groupnorm_apply_nhwc(const float* x1, int C1, const float* pa
                                         void* raw_bf16, float* stats, bsi_stream_t stream) {
     BSI_CHECK_ARG(x1 && part1 && gamma && beta && out_bf16 && B > 0 && HW > 0, "bsi_groupnorm_apply_nhwc: bad args");
     const int C = C1 + C2;
-    BSI_CHECK_ARG((C == 128 || C == 256) && C1 % (C / 32) == 0 && C1 % 4 == 0 && C2 % 4 == 0 && (C2 == 0 || (x2 && part2)),
-                  "bsi_groupnorm_apply_nhwc: C1=%d C2=%d unsupported (128 or 256 channels in all, groups within one tensor)", C1, C2);
+    BSI_CHECK_ARG((C == 128 || C == 256 || (C == 512 && C1 == 256)) && C1 % (C / 32) == 0 && C1 % 4 == 0 && C2 % 4 == 0 && (C2 == 0 || (x2 && part2)),
+                  "bsi_groupnorm_apply_nhwc: C1=%d C2=%d unsupported (128, 256 or 256 + 256 channels in all, groups within one tensor)", C1, C2);
     BSI_CHECK_ARG(HW % 128 == 0, "bsi_groupnorm_apply_nhwc: H*W=%d must be a multiple of 128 (the partials' block)", HW);
     __bf16* o = reinterpret_cast<__bf16*>(out_bf16);
     __bf16* r = reinterpret_cast<__bf16*>(raw_bf16);
@@ -452,8 +453,11 @@ extern "C" int bsi_groupnorm_apply_nhwc(const float* x1, int C1, const float* pa
         if (C == 128)
             hipLaunchKernelGGL((groupnorm_apply_kernel<128, ACT>), grid, dim3(GA_TPB), 0, S(stream), x1, C1, part1, x2, part2, HW, gamma, beta, eps,
                                silu, o, r, stats);
-        else
+        else if (C == 256)
             hipLaunchKernelGGL((groupnorm_apply_kernel<256, ACT>), grid, dim3(GA_TPB), 0, S(stream), x1, C1, part1, x2, part2, HW, gamma, beta, eps,
+                               silu, o, r, stats);
+        else  // cat(x, skip) at dim 256: a group of 16 channels = 4 units of one source, merged in the same fixed order
+            hipLaunchKernelGGL((groupnorm_apply_kernel<512, ACT>), grid, dim3(GA_TPB), 0, S(stream), x1, C1, part1, x2, part2, HW, gamma, beta, eps,
                                silu, o, r, stats);
         BSI_CHECK_LAUNCH("bsi_groupnorm_apply_nhwc");
         return BSI_OK;

@@ -229,12 +229,12 @@ int gemm(const void* A, int lda, const void* W, int ldw, const float* bias, void
 }
 
 int check_geometry(const bsi_unet_config* cfg, const UD& d, const char* who) {
-    BSI_CHECK_ARG((cfg->dim == 64 || cfg->dim == 128) && cfg->dim % cfg->heads == 0 && (d.dh == 16 || d.dh == 32 || d.dh == 64 || d.dh == 128) && d.HW % 64 == 0 &&
+    BSI_CHECK_ARG((cfg->dim == 64 || cfg->dim == 128 || cfg->dim == 256) && cfg->dim % cfg->heads == 0 && (d.dh == 16 || d.dh == 32 || d.dh == 64 || d.dh == 128) && d.HW % 64 == 0 &&
                       cfg->emb_size <= 64 && cfg->emb_size % 2 == 0 && cfg->c_dim % 64 == 0,
                   "%s: unsupported geometry dim=%d heads=%d HW=%d emb=%d c_dim=%d", who, cfg->dim, cfg->heads, d.HW, cfg->emb_size,
                   cfg->c_dim);
-    BSI_CHECK_ARG(cfg->block_heads == 0 || (cfg->block_heads > 0 && cfg->dim == 32 * cfg->block_heads),
-                  "%s: per-block attention needs head dim 32 (dim=%d, block_heads=%d)", who, cfg->dim, cfg->block_heads);
+    BSI_CHECK_ARG(cfg->block_heads == 0 || (cfg->block_heads > 0 && (cfg->dim == 32 * cfg->block_heads || (cfg->dim == 256 && cfg->block_heads == 4))),
+                  "%s: per-block attention needs head dim 32, or 64 at dim 256 (dim=%d, block_heads=%d)", who, cfg->dim, cfg->block_heads);
     return BSI_OK;
 }
 

@@ -68,10 +68,12 @@ class SimplifiedUNet(nn.Module):
 class DenoisingVDMUNet(nn.Module):
     """U-Net as in the VDM paper without down-sampling — same constructor as bsi.models.vdm_unet.DenoisingVDMUNet.
 
-    `n_attention_heads` (the centre Attention2D) runs natively for every count whose head dim `dim // n_attention_heads` is 16, 32, 64
-    or 128 (dim 128: 1, 2, 4, 8 heads; dim 64: 1, 2, 4).  As in the reference the constructor accepts any count; another head dim fails
-    at the first forward / sample / elbo / train_loss with the engine's `unsupported geometry` message.  The state dict does not
-    depend on the head count."""
+    The engines run `dim` 64, 128 and 256.  `n_attention_heads` (the centre Attention2D) runs natively for every count whose head dim
+    `dim // n_attention_heads` is 16, 32, 64 or 128 (dim 256: 2, 4, 8, 16 heads; dim 128: 1, 2, 4, 8; dim 64: 1, 2, 4).  There is no
+    head-dim-256 kernel, so dim 256 with 1 head does not run.  As in the reference the constructor accepts any width and any count;
+    another width or head dim fails at the first forward / sample / elbo / train_loss with the engine's `unsupported geometry`
+    message.  `downsampling_attention=True` (4 heads per block) runs at dim 128 and dim 256.  The state dict does not depend on the
+    head count."""
 
     def __init__(self, data_shape, pos_emb: NyquistPositionalEmbedding, actfn: str, dim: int, levels: int,
                  pos_emb_mult: int, n_attention_heads: int = 1, dropout: float | None = None,
@@ -86,10 +88,10 @@ class DenoisingVDMUNet(nn.Module):
         if padding_mode != "zeros":
             raise NotImplementedError("bsi_amd.DenoisingVDMUNet: the native kernels implement padding_mode='zeros' (the reference's "
                                       "configuration)")
-        if downsampling_attention and dim != 128:
-            raise NotImplementedError(f"bsi_amd.DenoisingVDMUNet: downsampling_attention=True needs dim=128 (the per-block "
+        if downsampling_attention and dim not in (128, 256):
+            raise NotImplementedError(f"bsi_amd.DenoisingVDMUNet: downsampling_attention=True needs dim=128 or dim=256 (the per-block "
                                       f"Attention2D has 4 heads; dim={dim} gives head dim {dim // 4}, and the engines run the per-block "
-                                      "attention at head dim 32 only)")
+                                      "attention at head dims 32 and 64 only)")
         n_channels = data_shape[0]
         in_features = out_features = n_channels
         if fourier_features is not None:

@@ -487,7 +487,9 @@ int bsi_conv_wgrad_bias_nhwc_bf16(const void* dy, int ldy, const void* x, const 
 int bsi_conv_wgrad_unpack(const float* packed, int Cout, int Cin, int taps, int cin_pad, int ld, int col0, int accumulate,
                           float* out, bsi_stream_t stream);
 /* GroupNorm(32 groups, affine, eps) over cat(x1, x2) channels (x2 nullable) per image, then activation `act` (BSI_ACT_*; 0 = none)
- * -> bf16 NHWC (residual_block.py:42-43, vdm_unet.py:52,84); raw_bf16 (nullable) receives the un-normalised bf16 copy. */
+ * -> bf16 NHWC (residual_block.py:42-43, vdm_unet.py:52,84); raw_bf16 (nullable) receives the un-normalised bf16 copy.
+ * C1 + C2 = 64, 128 or 256, or C1 = C2 = 256 (the up block's cat(x, skip) at dim 256: 16 channels per group); the backward entries
+ * take the same channel counts. */
 int bsi_groupnorm_nhwc(const float* x1, int C1, const float* x2, int C2, int B, int HW, const float* gamma,
                        const float* beta, float eps, int act, void* out_bf16, void* raw_bf16, bsi_stream_t stream);
 /* Same, and saves (mean, rstd) of every (image, group) to stats[B][32][2] for the backward pass (H*W <= 1024). */
@@ -495,7 +497,8 @@ int bsi_groupnorm_stats_nhwc(const float* x1, int C1, const float* x2, int C2, i
                              float eps, int act, void* out_bf16, void* raw_bf16, float* stats, bsi_stream_t stream);
 /* The same GroupNorm as ONE streaming pass: the statistics come from the partials the producing convolutions wrote
  * (bsi_conv_args::gn_partial: part1 [B*HW/128][C1/4][2], part2 [B*HW/128][C2/4][2] = (mean, M2) of 128 pixels x 4 channels),
- * merged per (image, group) in a fixed order, so x is read once and never held.  C1 + C2 = 128 or 256, H*W % 128 == 0;
+ * merged per (image, group) in a fixed order, so x is read once and never held.  C1 + C2 = 128 or 256, or C1 = C2 = 256 (a group of
+ * 16 channels = 4 units of one source); H*W % 128 == 0;
  * stats (nullable) receives (mean, rstd) as bsi_groupnorm_stats_nhwc writes them. */
 int bsi_groupnorm_apply_nhwc(const float* x1, int C1, const float* part1, const float* x2, int C2, const float* part2, int B, int HW,
                              const float* gamma, const float* beta, float eps, int act, void* out_bf16, void* raw_bf16,
@@ -517,7 +520,7 @@ int bsi_groupnorm_bwd_cast_nhwc(const void* da, const float* x1, int C1, const f
 /* Training form of the FiLM stage (residual_block.py:21-24,44-46): y = Dropout_p(SiLU(h1*(scale+1)+shift)), h1 and y bf16
  * [M, N], film fp32 rows (scale at [0,N), shift at [N,2N)) selected by (m / HW) % film_rows; the dropout mask is the
  * counter hash of (seed, site, row m, column n) (bsi_dropout_mask exports the same mask).  _bwd: dh1 = bf16(dU*(scale+1)) with
- * dU = dy*mask/(1-p)*silu'(u); dfilm[b, n] += sum dU*h1, dfilm[b, N+n] += sum dU (atomics; N 64 or 128, HW % 64 == 0). */
+ * dU = dy*mask/(1-p)*silu'(u); dfilm[b, n] += sum dU*h1, dfilm[b, N+n] += sum dU (atomics; N 64, 128 or 256, HW % 64 == 0). */
 int bsi_film_silu(const void* h1, int M, int N, int HW, const float* film, int film_rows, int film_stride, float dropout_p,
                   unsigned long long seed, unsigned site, void* y, bsi_stream_t stream);
 int bsi_film_silu_bwd(const void* dy, const void* h1, int M, int N, int HW, const float* film, int film_rows, int film_stride,
@@ -541,12 +544,14 @@ int bsi_unet_decode(const float* h, int B, int HW, int C, const float* w, const 
  * [ResBlock, Residual(GroupNorm -> Attention2D), ResBlock], levels blocks up on cat(x, skip)). */
 typedef struct bsi_unet_config {
     int C, H, W;      /* data_shape */
-    int dim, levels, heads;   /* dim 64 or 128; heads = n_attention_heads of the centre Attention2D: dim / heads in {16, 32, 64, 128} */
+    int dim, levels, heads;   /* dim 64, 128 or 256; heads = n_attention_heads of the centre Attention2D: dim / heads in {16, 32, 64, 128}
+                               * (no head dim 256: dim 256 runs 2, 4, 8 or 16 heads) */
     int ff_nmin, ff_nmax;
     int emb_size;     /* pos_emb.size (32) */
     int c_dim;        /* pos_emb.size * pos_emb_mult (128) */
     int block_heads;  /* downsampling_attention (residual_block.py:50-64): Residual(GroupNorm -> Attention2D(heads=block_heads)) after
-                       * EVERY residual block; 0 = none.  Head dim dim/block_heads must be 32 (dim 128, 4 heads). */
+                       * EVERY residual block; 0 = none.  Head dim dim/block_heads must be 32, or 64 at dim 256 with 4 heads
+                       * (the model passes 4: dim 128 or 256). */
 } bsi_unet_config;
 typedef struct bsi_unet_resblock_weights {
     const float *gn_w, *gn_b;                  /* layers.0: GroupNorm(32, Cin) */
@@ -573,6 +578,9 @@ typedef struct bsi_unet_weights {
                  * attention or its GroupNorm.  Workspace and tape sizes do not depend on it. */
 } bsi_unet_weights;
 int bsi_unet_cin_pad(const bsi_unet_config* cfg);
+/* Bytes of bsi_unet_forward's workspace for this configuration and batch; needs no device.  Always ask this function for the very
+ * configuration that will run: the size is not to be derived from that of another width (at dim 256 it is no less than twice
+ * the dim-128 value at the same B and image). */
 size_t bsi_unet_workspace_bytes(const bsi_unet_config* cfg, int B);
 size_t bsi_unet_film_scratch_bytes(const bsi_unet_config* cfg, int rows);
 /* film[r, blk, 0:2*dim] = project_onto_scale_shift_blk(pos_map(t[r]))  (fp32 [rows, nblocks, 2*dim]). */

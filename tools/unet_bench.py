@@ -5,6 +5,8 @@
 channels; the GFLOP figure then counts only the default UNet's work).  --train N: also time N train_loss backward steps (B images).
 --actfn NAME: the model's activation (silu, the default, gelu, relu, softplus, tanh).
 --heads N: n_attention_heads of the centre Attention2D (1, the default, 2, 4 or 8: head dims 128 .. 16).
+--dim N: the UNet's width (128, the default, 64 or 256; the GFLOP figure is that of dim 128 and is printed for dim 128 only).  Dim 256
+has no 1-head centre attention (head dim 256): give --heads 2, 4, 8 or 16.
 """
 import argparse
 import os
@@ -24,13 +26,14 @@ ap.add_argument("--downsampling-attention", action="store_true")
 ap.add_argument("--heads", type=int, default=1, metavar="N")
 ap.add_argument("--train", type=int, default=0, metavar="N")
 ap.add_argument("--actfn", default="silu", choices=("silu", "gelu", "relu", "softplus", "tanh"))
+ap.add_argument("--dim", type=int, default=128, metavar="N")
 args = ap.parse_args()
 B = int(os.environ.get("B", "256"))
 K = int(os.environ.get("K", "128"))
 dev = torch.device("cuda", 0)
 shape = (3, 32, 32)
 torch.manual_seed(0)
-m = DenoisingVDMUNet(shape, NyquistPositionalEmbedding(32, 100), args.actfn, 128, 32, 4, n_attention_heads=args.heads, dropout=0.1,
+m = DenoisingVDMUNet(shape, NyquistPositionalEmbedding(32, 100), args.actfn, args.dim, 32, 4, n_attention_heads=args.heads, dropout=0.1,
                      downsampling_attention=args.downsampling_attention,
                      fourier_features=FourierFeatures(n_min=6, n_max=8)).to(dev).eval()
 bsi = BSI(m, data_shape=shape, lambda_0=1e-2, alpha_M=1e6, alpha_R=2e6, k=K, preconditioning="edm",
@@ -45,8 +48,9 @@ with torch.no_grad():
     dt = time.perf_counter() - t0
 assert torch.isfinite(out).all()
 tag = (" downsampling_attention" if args.downsampling_attention else "") + (f" actfn={args.actfn}" if args.actfn != "silu" else "") + (
-    f" heads={args.heads}" if args.heads != 1 else "")
-print(f"UNet{tag} BSI.sample k={K} B={B}: {B / dt:.2f} images/s, {B / dt * (K + 1) * 53.47 / 1e3:.0f} model TFLOP/s")
+    f" heads={args.heads}" if args.heads != 1 else "") + (f" dim={args.dim}" if args.dim != 128 else "")
+flops = f", {B / dt * (K + 1) * 53.47 / 1e3:.0f} model TFLOP/s" if args.dim == 128 else ""
+print(f"UNet{tag} BSI.sample k={K} B={B}: {B / dt:.2f} images/s{flops}")
 if args.train:
     m.train()
     x = torch.rand((B, *shape), device=dev) * 2 - 1
