@@ -47,6 +47,42 @@ __global__ void nyquist_kernel(const float* __restrict__ t, int rows, const floa
     }
 }
 
+// The __shfl_xor butterfly of wave_sum (levels 32, 16, 8, 4, 2, 1: every lane ends with the same fixed tree over the 64 lanes,
+// because an IEEE addition is commutative bit for bit) on the lane-swap / DPP path, and for SEVERAL values at once: at a level
+// that pairs lane i with lane i ^ m, the lanes with bit m clear need only go on with value A and the others with value B, so
+// one v_permlane32_swap / v_permlane16_swap hands each half what it keeps and ONE addition per lane serves both values
+// (fold32 / fold16: `own + received` below the bit, `received + own` above it).  Every sum is the tree wave_sum builds.
+typedef unsigned u2v_ __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ float fold32(float a, float b) {  // lanes 0..31: level 32 of a, lanes 32..63: of b
+    const u2v_ t = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(b), false, false);
+    return __uint_as_float(t[0]) + __uint_as_float(t[1]);
+}
+__device__ __forceinline__ float fold16(float a, float b) {  // even 16-lane rows: level 16 of a, odd rows: of b
+    const u2v_ t = __builtin_amdgcn_permlane16_swap(__float_as_uint(a), __float_as_uint(b), false, false);
+    return __uint_as_float(t[0]) + __uint_as_float(t[1]);
+}
+// levels 8, 4, 2, 1 of ONE value inside each 16-lane row.  row_ror:4 stands for the xor with 4: after level 8 the lanes i and
+// i ^ 8 hold the same bits, and i + 4 is i ^ 4 or (i ^ 4) ^ 8.
+__device__ __forceinline__ float row16_tree(float v) {
+    v = dpp_xadd<0x128>(v);  // row_ror:8
+    v = dpp_xadd<0x124>(v);  // row_ror:4
+    v = dpp_xadd<0x4E>(v);   // quad_perm [2,3,0,1]
+    return dpp_xadd<0xB1>(v);  // quad_perm [1,0,3,2]
+}
+__device__ __forceinline__ float lane_bcast(float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); }
+// wave_sum of two / four values (all lanes must be active)
+__device__ __forceinline__ void wave_sum_x2(float& a, float& b) {
+    float t = fold32(a, b);
+    t = row16_tree(fold16(t, t));
+    a = lane_bcast(t, 0);
+    b = lane_bcast(t, 32);
+}
+__device__ __forceinline__ void wave_sum_x4(float (&s)[4]) {
+    const float t = row16_tree(fold16(fold32(s[0], s[2]), fold32(s[1], s[3])));  // 16-lane row r holds the sum of s[r]
+#pragma unroll
+    for (int r = 0; r < 4; ++r) s[r] = lane_bcast(t, 16 * r);
+}
+
 // One wave per row.  LayerNorm statistics in fp32 (two-pass over registers), then
 // out = fma(1 + scale, (x - mean) * rstd, shift)   (dit.py:50-55: addcmul(shift, scale + 1, norm(x)))
 // or, without modulation, the affine LayerNorm  normed * w + b  (dit.py:163).
@@ -270,6 +306,112 @@ __global__ __launch_bounds__(256) void ln_modulate_stream_kernel(float* __restri
     }
 }
 
+// The inference passes on the whole chip (one shared modulation row, no dropout, no statistics, 256 < d <= 1024): two ADJACENT rows
+// per wave.  All loads of both rows are in flight before the first reduction (twice the bytes per wave of ln_modulate_kernel), each
+// of the four modulation vectors is read once per wave for both rows, the two rows' sums share one lane-swap reduction
+// (wave_sum_x2: the tree of wave_sum), and what is not touched again for a millisecond -- the residual row, read and written, and
+// the deltas -- carries the non-temporal hint.  The normalised row does NOT: the GEMM that follows reads it at once.  Measured inside
+// the engine at 512 images, ms per sampling call over the 6192 passes (parent 1548-1553): this form 1415-1418; with the hint on
+// the normalised row as well 1529; without it on the residual row 1492, on its loads only 1469; one row per wave with every hint
+// 1676.  The hint on the residual row's store is also what the qkv GEMM behind the pass likes (2048-2050 ms against 2093-2099).
+// Arithmetic, operand order and rounding per element are those of ln_modulate_kernel: results are bit-identical.  `delta` may alias
+// `out`: a wave has read both its rows before it writes either.
+constexpr int LN_RPW = 2;
+template <int VPL>
+__global__ __launch_bounds__(256) void ln_modulate_rows_kernel(float* x, int M, int d, float eps, const float* __restrict__ shift,
+                                                               const float* __restrict__ scale, const __bf16* delta0,
+                                                               const float* __restrict__ gate0, const __bf16* delta,
+                                                               const float* __restrict__ gate, int write_x, __bf16* out) {
+    constexpr int RPW = LN_RPW;
+    const int lane = threadIdx.x & 63;
+    const int row0 = (blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) * RPW;
+    if (row0 >= M) return;
+    const int d4 = d >> 2;
+    const bool has0 = delta0 != nullptr, has1 = delta != nullptr;
+    f32x4 v[RPW][VPL];
+    u32x2 a[RPW][VPL], b[RPW][VPL];
+#pragma unroll
+    for (int j = 0; j < RPW; ++j) {
+        const int r = row0 + j < M ? row0 + j : M - 1;  // an odd M: the last wave reads its one row twice and stores it once
+#pragma unroll
+        for (int i = 0; i < VPL; ++i) {
+            const int c = i * 64 + lane;
+            v[j][i] = (c < d4) ? __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(x + (size_t)r * d) + c) : f32x4{0.f, 0.f, 0.f, 0.f};
+            if (has0 && c < d4) a[j][i] = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(delta0 + (size_t)r * d) + c);
+            if (has1 && c < d4) b[j][i] = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(delta + (size_t)r * d) + c);
+        }
+    }
+    float s[RPW];
+#pragma unroll
+    for (int j = 0; j < RPW; ++j) s[j] = 0.f;
+#pragma unroll
+    for (int i = 0; i < VPL; ++i) {
+        const int c = i * 64 + lane;
+        if (has0 && c < d4) {
+            const f32x4 g = reinterpret_cast<const f32x4*>(gate0)[c];
+#pragma unroll
+            for (int j = 0; j < RPW; ++j) {
+                v[j][i][0] = __fmaf_rn(g[0], __uint_as_float(a[j][i][0] << 16), v[j][i][0]);
+                v[j][i][1] = __fmaf_rn(g[1], __uint_as_float(a[j][i][0] & 0xffff0000u), v[j][i][1]);
+                v[j][i][2] = __fmaf_rn(g[2], __uint_as_float(a[j][i][1] << 16), v[j][i][2]);
+                v[j][i][3] = __fmaf_rn(g[3], __uint_as_float(a[j][i][1] & 0xffff0000u), v[j][i][3]);
+            }
+        }
+        if (has1 && c < d4) {
+            const f32x4 g = reinterpret_cast<const f32x4*>(gate)[c];
+#pragma unroll
+            for (int j = 0; j < RPW; ++j) {
+                v[j][i][0] = __fmaf_rn(g[0], __uint_as_float(b[j][i][0] << 16), v[j][i][0]);
+                v[j][i][1] = __fmaf_rn(g[1], __uint_as_float(b[j][i][0] & 0xffff0000u), v[j][i][1]);
+                v[j][i][2] = __fmaf_rn(g[2], __uint_as_float(b[j][i][1] << 16), v[j][i][2]);
+                v[j][i][3] = __fmaf_rn(g[3], __uint_as_float(b[j][i][1] & 0xffff0000u), v[j][i][3]);
+                if (write_x && row0 + j < M) __builtin_nontemporal_store(v[j][i], reinterpret_cast<f32x4*>(x + (size_t)(row0 + j) * d) + c);
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < RPW; ++j) s[j] += (v[j][i][0] + v[j][i][1]) + (v[j][i][2] + v[j][i][3]);
+    }
+    float q[RPW];
+    wave_sum_x2(s[0], s[1]);
+#pragma unroll
+    for (int j = 0; j < RPW; ++j) {
+        s[j] = s[j] / (float)d;  // mean
+        q[j] = 0.f;
+#pragma unroll
+        for (int i = 0; i < VPL; ++i) {
+            const int c = i * 64 + lane;
+            if (c < d4) {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const float dd = v[j][i][k] - s[j];
+                    q[j] = __fmaf_rn(dd, dd, q[j]);
+                }
+            }
+        }
+    }
+    wave_sum_x2(q[0], q[1]);
+#pragma unroll
+    for (int j = 0; j < RPW; ++j) q[j] = 1.0f / sqrtf(q[j] / (float)d + eps);  // rstd
+#pragma unroll
+    for (int i = 0; i < VPL; ++i) {
+        const int c = i * 64 + lane;
+        if (c < d4) {
+            const f32x4 sh = reinterpret_cast<const f32x4*>(shift)[c];
+            const f32x4 sc = reinterpret_cast<const f32x4*>(scale)[c];
+#pragma unroll
+            for (int j = 0; j < RPW; ++j) {
+                f32x4 y;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) y[k] = __fmaf_rn(sc[k] + 1.0f, (v[j][i][k] - s[j]) * q[j], sh[k]);
+                u32x2 w;
+                w[0] = pack_bf16x2(y[0], y[1]);
+                w[1] = pack_bf16x2(y[2], y[3]);
+                if (row0 + j < M) reinterpret_cast<u32x2*>(out + (size_t)(row0 + j) * d)[c] = w;
+            }
+        }
+    }
+}
+
 // fourier_features.py:21-36 standalone: x [outer, C, inner] -> out [outer, C*nfreq*2, inner],
 // channel (c*nfreq + n)*2 + o holds sin(offset_o + coef_n * x[c]).
 __global__ void fourier_features_kernel(const float* __restrict__ x, size_t total, int C, int inner, int nmin,
@@ -363,9 +505,9 @@ __global__ void dit_final_kernel(const float* __restrict__ x, int Mtok, int d, i
 #pragma unroll
             for (int i = 0; i < VPL; ++i) {
                 const int c = i * 64 + lane;
-                v[r][i] = (c < d4) ? reinterpret_cast<const f32x4*>(xr)[c] : f32x4{0.f, 0.f, 0.f, 0.f};
+                v[r][i] = (c < d4) ? __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(xr) + c) : f32x4{0.f, 0.f, 0.f, 0.f};
                 if (delta && c < d4) {  // pending gated residual of the last block's MLP branch (dit.py:98-102)
-                    const u32x2 dw = reinterpret_cast<const u32x2*>(delta + (size_t)row * d)[c];
+                    const u32x2 dw = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(delta + (size_t)row * d) + c);
                     const f32x4 g = reinterpret_cast<const f32x4*>(gate + (size_t)(b_idx % gate_rows) * gate_stride)[c];
                     v[r][i][0] = __fmaf_rn(g[0], __uint_as_float(dw[0] << 16), v[r][i][0]);
                     v[r][i][1] = __fmaf_rn(g[1], __uint_as_float(dw[0] & 0xffff0000u), v[r][i][1]);
@@ -375,10 +517,7 @@ __global__ void dit_final_kernel(const float* __restrict__ x, int Mtok, int d, i
                 s[r] += (v[r][i][0] + v[r][i][1]) + (v[r][i][2] + v[r][i][3]);
             }
         }
-#pragma unroll
-        for (int m = 32; m > 0; m >>= 1)
-#pragma unroll
-            for (int r = 0; r < FR; ++r) s[r] += __shfl_xor(s[r], m, 64);
+        wave_sum_x4(s);
 #pragma unroll
         for (int r = 0; r < FR; ++r) {
             const float mean = s[r] / (float)d;
@@ -396,10 +535,7 @@ __global__ void dit_final_kernel(const float* __restrict__ x, int Mtok, int d, i
                 }
             }
         }
-#pragma unroll
-        for (int m = 32; m > 0; m >>= 1)
-#pragma unroll
-            for (int r = 0; r < FR; ++r) q[r] += __shfl_xor(q[r], m, 64);
+        wave_sum_x4(q);
 #pragma unroll
         for (int i = 0; i < VPL; ++i) {
             const int c = i * 64 + lane;
@@ -414,56 +550,68 @@ __global__ void dit_final_kernel(const float* __restrict__ x, int Mtok, int d, i
                 }
             }
         }
-        float mine[FR] = {0.f, 0.f, 0.f, 0.f};
-        for (int o0 = 0; o0 < P; o0 += 4) {  // P <= 64: lane o keeps output o
-            float acc[FR][4];
+        // Decoder: 16 outputs per round, four groups of four.  A group's FR x 4 = 16 partial sums go down ONE shared xor tree: at
+        // each of the first four levels a lane keeps the half of the values that its lane bit selects and hands over the other
+        // half, so the group costs 8 + 4 + 2 + 1 + 1 + 1 = 17 exchanges and additions instead of 16 x 6, and each sum is still the
+        // tree of wave_sum over the 64 lanes' partial sums (same fma order per lane in front of it).  Afterwards lane L holds
+        // token L >> 4, output (L >> 2) & 3 of the group; lanes with L & 3 == group keep it, so after a round lane L owns
+        // output o0 + 4 (L & 3) + ((L >> 2) & 3) of token L >> 4 and stores it.
+        const bool b3 = (lane & 8) != 0, b2 = (lane & 4) != 0;
+        for (int o0 = 0; o0 < P; o0 += 16) {
+            float mine = 0.f;
 #pragma unroll
-            for (int r = 0; r < FR; ++r)
-#pragma unroll
-                for (int u = 0; u < 4; ++u) acc[r][u] = 0.f;
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int o = o0 + u < P ? o0 + u : P - 1;
-#pragma unroll
-                for (int i = 0; i < VPL; ++i) {
-                    const int c = i * 64 + lane;
-                    if (c < d4) {
-                        const f32x4 wv = WLDS ? reinterpret_cast<const f32x4*>(wsm + (size_t)o * d)[c]
-                                              : reinterpret_cast<const f32x4*>(dec_w + (size_t)o * d)[c];
-#pragma unroll
-                        for (int r = 0; r < FR; ++r)
-#pragma unroll
-                            for (int k = 0; k < 4; ++k) acc[r][u] = __fmaf_rn(v[r][i][k], wv[k], acc[r][u]);
-                    }
-                }
-            }
-#pragma unroll
-            for (int m = 32; m > 0; m >>= 1)
+            for (int grp = 0; grp < 4; ++grp) {
+                const int ob = o0 + 4 * grp;
+                if (ob >= P) break;
+                float acc[FR][4];
 #pragma unroll
                 for (int r = 0; r < FR; ++r)
 #pragma unroll
-                    for (int u = 0; u < 4; ++u) acc[r][u] += __shfl_xor(acc[r][u], m, 64);
+                    for (int u = 0; u < 4; ++u) acc[r][u] = 0.f;
 #pragma unroll
-            for (int u = 0; u < 4; ++u)
-                if (o0 + u < P && lane == o0 + u) {
+                for (int u = 0; u < 4; ++u) {
+                    const int o = ob + u < P ? ob + u : P - 1;
 #pragma unroll
-                    for (int r = 0; r < FR; ++r) mine[r] = acc[r][u] + dec_b[o0 + u];
+                    for (int i = 0; i < VPL; ++i) {
+                        const int c = i * 64 + lane;
+                        if (c < d4) {
+                            const f32x4 wv = WLDS ? reinterpret_cast<const f32x4*>(wsm + (size_t)o * d)[c]
+                                                  : reinterpret_cast<const f32x4*>(dec_w + (size_t)o * d)[c];
+#pragma unroll
+                            for (int r = 0; r < FR; ++r)
+#pragma unroll
+                                for (int k = 0; k < 4; ++k) acc[r][u] = __fmaf_rn(v[r][i][k], wv[k], acc[r][u]);
+                        }
+                    }
                 }
-        }
-        if (lane < P) {
-            const int intra = lane / C, ch = lane % C;
+                float a4[4];  // level 32: tokens (0, 2) and (1, 3); level 16: the two survivors -> token 2 * bit5 + bit4 = L >> 4
 #pragma unroll
-            for (int r = 0; r < FR; ++r) {
-                const int row = row0 + r;
-                if (row >= Mtok) break;
+                for (int u = 0; u < 4; ++u) a4[u] = fold16(fold32(acc[0][u], acc[2][u]), fold32(acc[1][u], acc[3][u]));
+                float a2[2];  // level 8: outputs (0, 2) and (1, 3)
+#pragma unroll
+                for (int u = 0; u < 2; ++u) {
+                    const float keep = b3 ? a4[u + 2] : a4[u], send = b3 ? a4[u] : a4[u + 2];
+                    a2[u] = keep + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(send), 0x128, 0xf, 0xf, true));  // row_ror:8
+                }
+                const float keep = b2 ? a2[1] : a2[0], send = b2 ? a2[0] : a2[1];  // level 4 -> output 2 * bit3 + bit2
+                float a1 = keep + __shfl_xor(send, 4, 64);
+                a1 = dpp_xadd<0x4E>(a1);  // levels 2 and 1
+                a1 = dpp_xadd<0xB1>(a1);
+                const int o = ob + ((lane >> 2) & 3);
+                if ((lane & 3) == grp && o < P) mine = a1 + dec_b[o];
+            }
+            const int o = o0 + 4 * (lane & 3) + ((lane >> 2) & 3);
+            const int row = row0 + (lane >> 4);
+            if (o < P && row < Mtok) {
+                const int intra = o / C, ch = o % C;
                 const int b_idx = row / tokens, tok = row % tokens;
                 const int th = tok / nw, tw = tok % nw;
                 const int hh = th * ps + intra / ps, ww = tw * ps + intra % ps;
                 const size_t gi = ((size_t)b_idx * C + ch) * HW + (size_t)hh * W + ww;
-                float rr = mine[r];
+                float rr = mine;
                 if (c_skip) {
                     const float cs = c_skip[(size_t)b_idx * coef_stride], co = c_out[(size_t)b_idx * coef_stride];
-                    rr = __fmaf_rn(co, mine[r], __fmul_rn(cs, mu[gi]));
+                    rr = __fmaf_rn(co, mine, __fmul_rn(cs, mu[gi]));
                 }
                 out[gi] = rr;
             }
@@ -558,6 +706,13 @@ int bsi_resid_ln_modulate_drop(float* x, int M, int d, float eps, const void* de
         if (g > (int)grid.x) g = (int)grid.x;
         hipLaunchKernelGGL(ln_modulate_stream_kernel<4>, dim3(g), dim3(TPB), 0, S(stream), x, M, d, eps, shift, scale, dl0, gate0, dl,
                            gate, write_x, o);
+        BSI_CHECK_LAUNCH("bsi_resid_ln_modulate");
+        return BSI_OK;
+    }
+    // the same passes on the whole chip: two adjacent rows per wave, the residual row and the deltas as non-temporal streams -- bit-identical
+    if (d > 256 && d <= 1024 && shift && o && mod_rows == 1 && !ln_w && !dc.thr && !x_out && !stats && !(maskw && mdc.thr)) {
+        hipLaunchKernelGGL(ln_modulate_rows_kernel<4>, dim3((M + wpb * LN_RPW - 1) / (wpb * LN_RPW)), dim3(TPB), 0, S(stream), x, M, d,
+                           eps, shift, scale, dl0, gate0, dl, gate, write_x, o);
         BSI_CHECK_LAUNCH("bsi_resid_ln_modulate");
         return BSI_OK;
     }
