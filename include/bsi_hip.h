@@ -145,7 +145,8 @@ int bsi_affine_noise(const float* x, const float* a, const float* b, const float
 /* vdm.py:365-379: out = a[idx]*z + b[idx]*xh + c[idx]*eps over n floats (one ancestral sampling step). */
 int bsi_axpbypcz(const float* z, const float* xh, const float* eps, const float* a, const float* b, const float* c, int idx, size_t n,
                  float* out, bsi_stream_t stream);
-/* bfn.py:291 (.clip) and its backward (gradient passes where lo <= raw <= hi). */
+/* bfn.py:291 (.clip) and its backward (gradient passes where lo <= raw <= hi).  A NaN input stays NaN, as in torch.clamp
+ * (the backward gives it gradient 0); every other input gives lo below lo, hi above hi and itself in between. */
 int bsi_clip(const float* x, float lo, float hi, size_t n, float* out, bsi_stream_t stream);
 int bsi_clip_bwd(const float* g, const float* raw, float lo, float hi, size_t n, float* out, bsi_stream_t stream);
 /* vdm.py:138-150,324-329: gamma = lerp(gamma_0, gamma_1, t); alpha = sqrt(sigmoid(-gamma)), sigma = sqrt(sigmoid(gamma)),
@@ -159,7 +160,8 @@ int bsi_vdm_step_coeffs(const float* t, int k, float gamma_0, float gamma_1, flo
 /* vdm.py:167-195: Normal(x_hat, std) evaluated at the k bin centres, normalised over bins; out[r] = -sum_D log p[bin(x)]. */
 int bsi_vdm_recon_nll(const float* x, const float* x_hat, float std_, const float* bounds, float lo_edge, float dx, int k, int rows,
                       int B, int D, float* out, bsi_stream_t stream);
-/* vdm.py:127-136: out[r] = 0.5 * sum_D (var_1 + (1 - var_1) x^2 - log var_1 - 1). */
+/* vdm.py:127-136: out[r] = 0.5 * sum_D (var_1 + (1 - var_1) x^2 - log var_1 - 1), summed as (1 - var_1) x^2 + c with the constant
+ * c = var_1 - 1 - log var_1 formed in fp64 (no cancellation against the 1: relative error within 4 D 2^-24). */
 int bsi_vdm_prior(const float* x, float var_1, int rows, int D, float* out, bsi_stream_t stream);
 /* bfn.py:282-309,197-198 per time t[i] (gamma = 1 - sigma_1^(2t)): fa = gamma, fb = sqrt(gamma(1-gamma)) (flow distribution);
  * c_skip = 1/g, c_out = -sqrt((1-g)/g) with g at max(t, t_min), both 0 where t < t_min (x_hat before the clip);

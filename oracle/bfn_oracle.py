@@ -35,7 +35,8 @@ class BFNOracle:
     # bfn.py:311-325 (low-discrepancy branch).  Draw order: rand(()), randperm(n*B)
     def t_grid(self, offset, perm, n, B):
         total = n * B
-        return torch.remainder((perm / (1 + total)).reshape(n, B) + offset, 1)
+        # the grid is an fp32 tensor whatever the module's dtype (perm / int); the cast keeps an fp64 oracle running on it
+        return torch.remainder((perm / (1 + total)).reshape(n, B) + offset, 1).to(self.dtype)
 
     # bfn.py:125-153.  Draw: randn(n, B, *shape)
     def reconstruction_loss(self, x, eps):
@@ -71,9 +72,11 @@ class BFNOracle:
         return 0.5 * n * (1 - (self.sigma_1 ** (2 / n))) * ((self.sigma_1 ** ((-2 / n) * (i + 1))) * err)
 
     # bfn.py:183-198.  Draw: rand(()), randperm(ns*B), randn(ns, B, *shape)
-    def continuous_time_loss(self, x, offset, perm, eps):
+    # With low_discrepancy_sampling=False the times are one rand((B, ns)) draw read as [ns, B] (bfn.py:327-329): pass it as `t`.
+    def continuous_time_loss(self, x, offset, perm, eps, t=None):
         ns, B = eps.shape[0], len(x)
-        t = self.t_grid(offset, perm, ns, B)
+        if t is None:
+            t = self.t_grid(offset, perm, ns, B)
         mu = self.flow_sample(x, t, eps)
         x_hat = self.predict_x(mu.flatten(end_dim=1), t.flatten(end_dim=1)).reshape(ns, B, *self.data_shape)
         err = (x - x_hat).square().reshape(ns, B, -1).sum(dim=2)

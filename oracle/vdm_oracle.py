@@ -56,7 +56,8 @@ class VDMOracle:
     # vdm.py:381-397 (low-discrepancy branch).  Draw order: rand(()), randperm(n*B)
     def t_grid(self, offset, perm, n, B):
         total = n * B
-        return torch.remainder((perm / (1 + total)).reshape(n, B) + offset, 1)
+        # the grid is an fp32 tensor whatever the module's dtype (perm / int); the cast keeps an fp64 oracle running on it
+        return torch.remainder((perm / (1 + total)).reshape(n, B) + offset, 1).to(self.dtype)
 
     # vdm.py:127-136
     def prior_loss(self, x):
@@ -100,9 +101,11 @@ class VDMOracle:
         return 0.5 * T * (self.snr(s_i) - self.snr(t_i)) * err
 
     # vdm.py:233-249.  Draw: rand(()), randperm(n*B), randn(n, B, *shape)
-    def inf_diffusion_loss(self, x, offset, perm, eps):
+    # With low_discrepancy_sampling=False the times are one rand((B, n)) draw read as [n, B] (vdm.py:399-401): pass it as `t`.
+    def inf_diffusion_loss(self, x, offset, perm, eps, t=None):
         n, B = eps.shape[0], len(x)
-        t = self.t_grid(offset, perm, n, B)
+        if t is None:
+            t = self.t_grid(offset, perm, n, B)
         z_t = self.zt_given_x(x, t, eps)
         x_hat = self.predict_x(z_t.flatten(end_dim=1), t.flatten(end_dim=1)).reshape(n, B, *self.data_shape)
         err = (x - x_hat).square().reshape(n, B, -1).sum(dim=2)

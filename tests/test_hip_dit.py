@@ -16,7 +16,7 @@ import torch
 
 from oracle import bsi_oracle as bo
 from oracle import dit_oracle as do
-from tests.util import bound, golden, max_rel, rel_linf, report, weights
+from tests.util import TinyConv, bound, golden, max_rel, rel_linf, report, weights
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -167,17 +167,7 @@ def test_sample_history_teacher_forced_and_free_running():
 def test_generic_model_path_tinyconv():
     """BSI around an arbitrary torch denoiser (the README Conv2d): fp32 end to end, wrapper kernels native."""
     g = golden("g4_train_tinyconv")
-
-    class Model(torch.nn.Module):
-        def __init__(self):
-            super().__init__()
-            self.layer = torch.nn.Conv2d(4, 3, 3, padding=1)
-
-        def forward(self, mu, t):
-            t = torch.movedim(t.expand((1, *mu.shape[-2:], len(t))), -1, 0)
-            return self.layer(torch.cat((mu, t), dim=-3))
-
-    m = Model()
+    m = TinyConv()
     m.load_state_dict({k[2:]: v for k, v in g.items() if k.startswith("W.")})
     m = m.to(DEV)
     bsi = make_bsi(m, (3, 8, 8))

@@ -38,6 +38,18 @@ def max_rel(a, b, floor=0.0):
     return float(((a - b).abs() / b.abs().clamp_min(floor if floor > 0 else 1e-30)).max())
 
 
+class TinyConv(torch.nn.Module):
+    """The README's generic denoiser: one Conv2d over the image with the time as a fourth channel."""
+
+    def __init__(self):
+        super().__init__()
+        self.layer = torch.nn.Conv2d(4, 3, 3, padding=1)
+
+    def forward(self, mu, t):
+        t = torch.movedim(t.expand((1, *mu.shape[-2:], len(t))), -1, 0)
+        return self.layer(torch.cat((mu, t), dim=-3))
+
+
 CALIB = dict(shape=(3, 32, 32), patch_size=4, dim=128, depth=4, heads=2, ff=(6, 8), seed=11, B=64)
 
 
