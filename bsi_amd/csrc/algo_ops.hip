@@ -14,7 +14,7 @@ constexpr int TPB = 256;
 inline dim3 row_grid(int rows, int D4) {
     int gx = (D4 + TPB - 1) / TPB;
     if (gx > 64) gx = 64;
-    return dim3(gx, rows);
+    return dim3(gx, rows < 32768 ? rows : 32768);  // grid.y has a hardware limit of 65535: the kernel strides over rows
 }
 
 __device__ __forceinline__ float softplus_f(float x) { return x > 20.0f ? x : log1pf(expf(x)); }  // torch threshold 20
@@ -33,18 +33,19 @@ __global__ void tgrid_kernel(const int64_t* perm, const float* offset, int total
 
 // out[r] = addcmul(a[r] * x[r % B], b[r], eps[r])   (vdm.py:343-347, bfn.py:302-309)
 __global__ void affine_noise_kernel(const float* __restrict__ x, const float* __restrict__ a, const float* __restrict__ b,
-                                    const float* __restrict__ eps, int B, int D4, float* __restrict__ out) {
-    const int r = blockIdx.y;
-    const float ar = a[r], br = b[r];
-    const f32x4* xr = reinterpret_cast<const f32x4*>(x) + (size_t)(r % B) * D4;
-    const f32x4* er = reinterpret_cast<const f32x4*>(eps) + (size_t)r * D4;
-    f32x4* o = reinterpret_cast<f32x4*>(out) + (size_t)r * D4;
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < D4; i += gridDim.x * blockDim.x) {
-        const f32x4 xv = xr[i], ev = er[i];
-        f32x4 v;
+                                    const float* __restrict__ eps, int rows, int B, int D4, float* __restrict__ out) {
+    for (int r = blockIdx.y; r < rows; r += gridDim.y) {  // grid.y is capped (row_grid)
+        const float ar = a[r], br = b[r];
+        const f32x4* xr = reinterpret_cast<const f32x4*>(x) + (size_t)(r % B) * D4;
+        const f32x4* er = reinterpret_cast<const f32x4*>(eps) + (size_t)r * D4;
+        f32x4* o = reinterpret_cast<f32x4*>(out) + (size_t)r * D4;
+        for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < D4; i += gridDim.x * blockDim.x) {
+            const f32x4 xv = xr[i], ev = er[i];
+            f32x4 v;
 #pragma unroll
-        for (int k = 0; k < 4; ++k) v[k] = __fmaf_rn(br, ev[k], __fmul_rn(ar, xv[k]));
-        o[i] = v;
+            for (int k = 0; k < 4; ++k) v[k] = __fmaf_rn(br, ev[k], __fmul_rn(ar, xv[k]));
+            o[i] = v;
+        }
     }
 }
 
@@ -239,7 +240,7 @@ extern "C" int bsi_tgrid(const int64_t* perm, const float* offset, int total, fl
 extern "C" int bsi_affine_noise(const float* x, const float* a, const float* b, const float* eps, int rows, int B, int D, float* out,
                                 bsi_stream_t stream) {
     BSI_CHECK_ARG(x && a && b && eps && out && rows > 0 && B > 0 && D > 0 && D % 4 == 0, "bsi_affine_noise: bad args");
-    hipLaunchKernelGGL(affine_noise_kernel, row_grid(rows, D / 4), dim3(TPB), 0, S(stream), x, a, b, eps, B, D / 4, out);
+    hipLaunchKernelGGL(affine_noise_kernel, row_grid(rows, D / 4), dim3(TPB), 0, S(stream), x, a, b, eps, rows, B, D / 4, out);
     BSI_CHECK_LAUNCH("bsi_affine_noise");
     return BSI_OK;
 }

@@ -55,7 +55,9 @@ __global__ void lambda_to_t_kernel(const float* lam, int n, float delta, float l
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     float l = lam[i];
-    if (t) t[i] = __fsub_rn(logf(l), ln_low) / delta;  // bsi.py:81
+    // bsi.py:81.  log(l) - ln_low cancels towards t = 0 (lambda is lambda_0 there): an ulp of the logarithm is 2.6e-8 of t, 2.6 % at
+    // t = 1e-6, so the logarithm is rounded correctly (through fp64: logf is an ulp off on some inputs); the op order stays
+    if (t) t[i] = __fsub_rn((float)log((double)l), ln_low) / delta;
     if (rpdf) rpdf[i] = __fmul_rn(l, delta);            // bsi.py:78
 }
 
@@ -79,88 +81,93 @@ __global__ void lambda_grid_kernel(const int64_t* perm, const float* offset, int
     lam[i] = icdf_f(t, delta, ln_low);
 }
 
-// rows x D elementwise kernels: grid.y = row, grid.x strides over D/4 float4 groups -----------------
+// rows x D elementwise kernels: grid.y strides over rows, grid.x strides over D/4 float4 groups -----------------
 __global__ void q_sample_kernel(const float* __restrict__ x, const float* __restrict__ lam,
-                                const float* __restrict__ eps, float lambda_0, int B, int D4, float* __restrict__ mu) {
-    const int r = blockIdx.y;
-    const float l = lam[r];
-    const float a = __fsub_rn(l, lambda_0) / l;  // (lam - lam0)/lam
-    const float s = rsqrt_rn(l);
-    const f32x4* xr = reinterpret_cast<const f32x4*>(x) + (size_t)(r % B) * D4;
-    const f32x4* er = reinterpret_cast<const f32x4*>(eps) + (size_t)r * D4;
-    f32x4* mr = reinterpret_cast<f32x4*>(mu) + (size_t)r * D4;
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < D4; i += gridDim.x * blockDim.x) {
-        f32x4 xv = xr[i], ev = er[i], o;
+                                const float* __restrict__ eps, float lambda_0, int rows, int B, int D4, float* __restrict__ mu) {
+    for (int r = blockIdx.y; r < rows; r += gridDim.y) {  // grid.y is capped (row_grid)
+        const float l = lam[r];
+        const float a = __fsub_rn(l, lambda_0) / l;  // (lam - lam0)/lam
+        const float s = rsqrt_rn(l);
+        const f32x4* xr = reinterpret_cast<const f32x4*>(x) + (size_t)(r % B) * D4;
+        const f32x4* er = reinterpret_cast<const f32x4*>(eps) + (size_t)r * D4;
+        f32x4* mr = reinterpret_cast<f32x4*>(mu) + (size_t)r * D4;
+        for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < D4; i += gridDim.x * blockDim.x) {
+            f32x4 xv = xr[i], ev = er[i], o;
 #pragma unroll
-        for (int c = 0; c < 4; ++c) o[c] = __fmaf_rn(s, ev[c], __fmul_rn(a, xv[c]));  // addcmul(a*x, s, eps)
-        mr[i] = o;
+            for (int c = 0; c < 4; ++c) o[c] = __fmaf_rn(s, ev[c], __fmul_rn(a, xv[c]));  // addcmul(a*x, s, eps)
+            mr[i] = o;
+        }
     }
 }
 
-__global__ void scale_rows_kernel(const float* __restrict__ mu, const float* __restrict__ c, int c_stride, int D4,
+__global__ void scale_rows_kernel(const float* __restrict__ mu, const float* __restrict__ c, int c_stride, int rows, int D4,
                                   float* __restrict__ out) {
-    const int r = blockIdx.y;
-    const float s = c[(size_t)r * c_stride];
-    const f32x4* mr = reinterpret_cast<const f32x4*>(mu) + (size_t)r * D4;
-    f32x4* o = reinterpret_cast<f32x4*>(out) + (size_t)r * D4;
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < D4; i += gridDim.x * blockDim.x) {
-        f32x4 v = mr[i];
+    for (int r = blockIdx.y; r < rows; r += gridDim.y) {  // grid.y is capped (row_grid)
+        const float s = c[(size_t)r * c_stride];
+        const f32x4* mr = reinterpret_cast<const f32x4*>(mu) + (size_t)r * D4;
+        f32x4* o = reinterpret_cast<f32x4*>(out) + (size_t)r * D4;
+        for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < D4; i += gridDim.x * blockDim.x) {
+            f32x4 v = mr[i];
 #pragma unroll
-        for (int k = 0; k < 4; ++k) v[k] = __fmul_rn(s, v[k]);
-        o[i] = v;
+            for (int k = 0; k < 4; ++k) v[k] = __fmul_rn(s, v[k]);
+            o[i] = v;
+        }
     }
 }
 
 // bsi.py:325: mu_0 = rsqrt(lam[0]) * eps0
-__global__ void sample_init_kernel(const float* __restrict__ eps0, const float* __restrict__ lam, int D4,
+__global__ void sample_init_kernel(const float* __restrict__ eps0, const float* __restrict__ lam, int rows, int D4,
                                    float* __restrict__ mu) {
-    const int r = blockIdx.y;
-    const float s = rsqrt_rn(lam[0]);
-    const f32x4* er = reinterpret_cast<const f32x4*>(eps0) + (size_t)r * D4;
-    f32x4* o = reinterpret_cast<f32x4*>(mu) + (size_t)r * D4;
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < D4; i += gridDim.x * blockDim.x) {
-        f32x4 v = er[i];
+    for (int r = blockIdx.y; r < rows; r += gridDim.y) {  // grid.y is capped (row_grid)
+        const float s = rsqrt_rn(lam[0]);
+        const f32x4* er = reinterpret_cast<const f32x4*>(eps0) + (size_t)r * D4;
+        f32x4* o = reinterpret_cast<f32x4*>(mu) + (size_t)r * D4;
+        for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < D4; i += gridDim.x * blockDim.x) {
+            f32x4 v = er[i];
 #pragma unroll
-        for (int k = 0; k < 4; ++k) v[k] = __fmul_rn(s, v[k]);
-        o[i] = v;
+            for (int k = 0; k < 4; ++k) v[k] = __fmul_rn(s, v[k]);
+            o[i] = v;
+        }
     }
 }
 
 __global__ void predict_combine_kernel(const float* __restrict__ mu, const float* __restrict__ f,
-                                       const float* __restrict__ cs, const float* __restrict__ co, int c_stride, int D4,
+                                       const float* __restrict__ cs, const float* __restrict__ co, int c_stride, int rows, int D4,
                                        float* __restrict__ xh) {
-    const int r = blockIdx.y;
-    const float a = cs[(size_t)r * c_stride], b = co[(size_t)r * c_stride];
-    const f32x4* mr = reinterpret_cast<const f32x4*>(mu) + (size_t)r * D4;
-    const f32x4* fr = reinterpret_cast<const f32x4*>(f) + (size_t)r * D4;
-    f32x4* o = reinterpret_cast<f32x4*>(xh) + (size_t)r * D4;
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < D4; i += gridDim.x * blockDim.x) {
-        f32x4 m = mr[i], fv = fr[i], v;
+    for (int r = blockIdx.y; r < rows; r += gridDim.y) {  // grid.y is capped (row_grid)
+        const float a = cs[(size_t)r * c_stride], b = co[(size_t)r * c_stride];
+        const f32x4* mr = reinterpret_cast<const f32x4*>(mu) + (size_t)r * D4;
+        const f32x4* fr = reinterpret_cast<const f32x4*>(f) + (size_t)r * D4;
+        f32x4* o = reinterpret_cast<f32x4*>(xh) + (size_t)r * D4;
+        for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < D4; i += gridDim.x * blockDim.x) {
+            f32x4 m = mr[i], fv = fr[i], v;
 #pragma unroll
-        for (int k = 0; k < 4; ++k) v[k] = __fmaf_rn(b, fv[k], __fmul_rn(a, m[k]));  // addcmul(c_skip*mu, c_out, f)
-        o[i] = v;
+            for (int k = 0; k < 4; ++k) v[k] = __fmaf_rn(b, fv[k], __fmul_rn(a, m[k]));  // addcmul(c_skip*mu, c_out, f)
+            o[i] = v;
+        }
     }
 }
 
 __global__ void predict_combine_bwd_kernel(const float* __restrict__ g, const float* __restrict__ cs,
-                                           const float* __restrict__ co, int c_stride, int D4, float* __restrict__ gf,
+                                           const float* __restrict__ co, int c_stride, int rows, int D4, float* __restrict__ gf,
                                            float* __restrict__ gmu) {
-    const int r = blockIdx.y;
-    const float a = cs[(size_t)r * c_stride], b = co[(size_t)r * c_stride];
-    const f32x4* gr = reinterpret_cast<const f32x4*>(g) + (size_t)r * D4;
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < D4; i += gridDim.x * blockDim.x) {
-        f32x4 gv = gr[i];
-        if (gf) {
-            f32x4 v;
+    for (int r = blockIdx.y; r < rows; r += gridDim.y) {  // grid.y is capped (row_grid)
+        const float a = cs[(size_t)r * c_stride], b = co[(size_t)r * c_stride];
+        const f32x4* gr = reinterpret_cast<const f32x4*>(g) + (size_t)r * D4;
+        for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < D4; i += gridDim.x * blockDim.x) {
+            f32x4 gv = gr[i];
+            if (gf) {
+                f32x4 v;
 #pragma unroll
-            for (int k = 0; k < 4; ++k) v[k] = b * gv[k];
-            (reinterpret_cast<f32x4*>(gf) + (size_t)r * D4)[i] = v;
-        }
-        if (gmu) {
-            f32x4 v;
+                for (int k = 0; k < 4; ++k) v[k] = b * gv[k];
+                (reinterpret_cast<f32x4*>(gf) + (size_t)r * D4)[i] = v;
+            }
+            if (gmu) {
+                f32x4 v;
 #pragma unroll
-            for (int k = 0; k < 4; ++k) v[k] = a * gv[k];
-            (reinterpret_cast<f32x4*>(gmu) + (size_t)r * D4)[i] = v;
+                for (int k = 0; k < 4; ++k) v[k] = a * gv[k];
+                (reinterpret_cast<f32x4*>(gmu) + (size_t)r * D4)[i] = v;
+            }
         }
     }
 }
@@ -295,18 +302,19 @@ __global__ void sqerr_rows_kernel(const float* __restrict__ x, const float* __re
 
 __global__ void sqerr_rows_bwd_kernel(const float* __restrict__ x, const float* __restrict__ xh,
                                       const float* __restrict__ w, const float* __restrict__ g, float scale, int mean,
-                                      int B, int D4, float* __restrict__ gx) {
-    const int r = blockIdx.y;
-    float coef = -2.0f * g[r] * (w ? w[r] : 1.0f) * scale;
-    if (mean) coef /= (float)(D4 * 4);
-    const f32x4* xr = reinterpret_cast<const f32x4*>(x) + (size_t)(r % B) * D4;
-    const f32x4* hr = reinterpret_cast<const f32x4*>(xh) + (size_t)r * D4;
-    f32x4* o = reinterpret_cast<f32x4*>(gx) + (size_t)r * D4;
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < D4; i += gridDim.x * blockDim.x) {
-        f32x4 a = xr[i], b = hr[i], v;
+                                      int rows, int B, int D4, float* __restrict__ gx) {
+    for (int r = blockIdx.y; r < rows; r += gridDim.y) {  // grid.y is capped (row_grid)
+        float coef = -2.0f * g[r] * (w ? w[r] : 1.0f) * scale;
+        if (mean) coef /= (float)(D4 * 4);
+        const f32x4* xr = reinterpret_cast<const f32x4*>(x) + (size_t)(r % B) * D4;
+        const f32x4* hr = reinterpret_cast<const f32x4*>(xh) + (size_t)r * D4;
+        f32x4* o = reinterpret_cast<f32x4*>(gx) + (size_t)r * D4;
+        for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < D4; i += gridDim.x * blockDim.x) {
+            f32x4 a = xr[i], b = hr[i], v;
 #pragma unroll
-        for (int k = 0; k < 4; ++k) v[k] = coef * (a[k] - b[k]);
-        o[i] = v;
+            for (int k = 0; k < 4; ++k) v[k] = coef * (a[k] - b[k]);
+            o[i] = v;
+        }
     }
 }
 
@@ -362,7 +370,7 @@ inline dim3 row_grid(int rows, int D4) {
     int gx = (D4 + TPB - 1) / TPB;
     if (gx > 64) gx = 64;
     if (gx < 1) gx = 1;
-    return dim3(gx, rows);
+    return dim3(gx, rows < 32768 ? rows : 32768);  // grid.y has a hardware limit of 65535: the kernels stride over rows
 }
 
 }  // namespace
@@ -409,7 +417,7 @@ extern "C" int bsi_q_sample(const bsi_params* p, const float* x, const float* la
                             int D, float* mu, bsi_stream_t stream) {
     BSI_CHECK_ARG(p && x && lam && eps && mu, "bsi_q_sample: null pointer");
     BSI_CHECK_ARG(rows > 0 && B > 0 && D > 0 && D % 4 == 0, "bsi_q_sample: rows=%d B=%d D=%d (D %% 4 must be 0)", rows, B, D);
-    hipLaunchKernelGGL(q_sample_kernel, row_grid(rows, D / 4), dim3(TPB), 0, S(stream), x, lam, eps, p->lambda_0, B,
+    hipLaunchKernelGGL(q_sample_kernel, row_grid(rows, D / 4), dim3(TPB), 0, S(stream), x, lam, eps, p->lambda_0, rows, B,
                        D / 4, mu);
     BSI_CHECK_LAUNCH("bsi_q_sample");
     return BSI_OK;
@@ -418,14 +426,14 @@ extern "C" int bsi_q_sample(const bsi_params* p, const float* x, const float* la
 extern "C" int bsi_scale_rows(const float* mu, const float* c, int c_stride, int rows, int D, float* out,
                               bsi_stream_t stream) {
     BSI_CHECK_ARG(mu && c && out && rows > 0 && D > 0 && D % 4 == 0, "bsi_scale_rows: bad args");
-    hipLaunchKernelGGL(scale_rows_kernel, row_grid(rows, D / 4), dim3(TPB), 0, S(stream), mu, c, c_stride, D / 4, out);
+    hipLaunchKernelGGL(scale_rows_kernel, row_grid(rows, D / 4), dim3(TPB), 0, S(stream), mu, c, c_stride, rows, D / 4, out);
     BSI_CHECK_LAUNCH("bsi_scale_rows");
     return BSI_OK;
 }
 
 extern "C" int bsi_sample_init(const float* eps0, const float* lam, int rows, int D, float* mu, bsi_stream_t stream) {
     BSI_CHECK_ARG(eps0 && lam && mu && rows > 0 && D > 0 && D % 4 == 0, "bsi_sample_init: bad args");
-    hipLaunchKernelGGL(sample_init_kernel, row_grid(rows, D / 4), dim3(TPB), 0, S(stream), eps0, lam, D / 4, mu);
+    hipLaunchKernelGGL(sample_init_kernel, row_grid(rows, D / 4), dim3(TPB), 0, S(stream), eps0, lam, rows, D / 4, mu);
     BSI_CHECK_LAUNCH("bsi_sample_init");
     return BSI_OK;
 }
@@ -434,7 +442,7 @@ extern "C" int bsi_predict_combine(const float* mu, const float* f, const float*
                                    int c_stride, int rows, int D, float* x_hat, bsi_stream_t stream) {
     BSI_CHECK_ARG(mu && f && c_skip && c_out && x_hat && rows > 0 && D > 0 && D % 4 == 0, "bsi_predict_combine: bad args");
     hipLaunchKernelGGL(predict_combine_kernel, row_grid(rows, D / 4), dim3(TPB), 0, S(stream), mu, f, c_skip, c_out,
-                       c_stride, D / 4, x_hat);
+                       c_stride, rows, D / 4, x_hat);
     BSI_CHECK_LAUNCH("bsi_predict_combine");
     return BSI_OK;
 }
@@ -443,7 +451,7 @@ extern "C" int bsi_predict_combine_bwd(const float* g, const float* c_skip, cons
                                        int D, float* g_f, float* g_mu, bsi_stream_t stream) {
     BSI_CHECK_ARG(g && c_skip && c_out && rows > 0 && D > 0 && D % 4 == 0, "bsi_predict_combine_bwd: bad args");
     hipLaunchKernelGGL(predict_combine_bwd_kernel, row_grid(rows, D / 4), dim3(TPB), 0, S(stream), g, c_skip, c_out,
-                       c_stride, D / 4, g_f, g_mu);
+                       c_stride, rows, D / 4, g_f, g_mu);
     BSI_CHECK_LAUNCH("bsi_predict_combine_bwd");
     return BSI_OK;
 }
@@ -517,7 +525,7 @@ extern "C" int bsi_sqerr_rows_bwd(const float* x, const float* x_hat, const floa
                                   int mean, int rows, int B, int D, float* g_xhat, bsi_stream_t stream) {
     BSI_CHECK_ARG(x && x_hat && g && g_xhat && rows > 0 && B > 0 && D > 0 && D % 4 == 0, "bsi_sqerr_rows_bwd: bad args");
     hipLaunchKernelGGL(sqerr_rows_bwd_kernel, row_grid(rows, D / 4), dim3(TPB), 0, S(stream), x, x_hat, w, g, scale,
-                       mean, B, D / 4, g_xhat);
+                       mean, rows, B, D / 4, g_xhat);
     BSI_CHECK_LAUNCH("bsi_sqerr_rows_bwd");
     return BSI_OK;
 }

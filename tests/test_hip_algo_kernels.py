@@ -7,7 +7,7 @@ import pytest
 import torch
 
 from tests import algo_cases as ac
-from tests.util import bound, report
+from tests.util import Out, bound, release, report
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -28,7 +28,7 @@ _KEEP = []  # device copies stay alive until the test ends (kernels are enqueued
 @pytest.fixture(autouse=True)
 def _release_device_copies():
     yield
-    torch.cuda.synchronize()
+    release()
     _KEEP.clear()
 
 
@@ -36,26 +36,6 @@ def dev(t):
     d = t.to(DEV).contiguous()
     _KEEP.append(d)
     return d
-
-
-class Out:
-    """n output floats followed by GUARD sentinel floats."""
-
-    def __init__(self, n):
-        self.n = n
-        self.full = torch.full((n + ac.GUARD,), ac.SENTINEL, dtype=F32, device=DEV)
-        _KEEP.append(self.full)
-
-    @property
-    def ptr(self):
-        from bsi_amd import _native
-        return _native.ptr(self.full)
-
-    def get(self):
-        """The output on the CPU, after checking that the kernel wrote every element and nothing behind them."""
-        h = self.full.cpu()
-        assert bool((h[self.n:] == ac.SENTINEL).all()), "the kernel wrote past the end of its output"
-        return h[:self.n].clone()
 
 
 def bits(t):

@@ -139,3 +139,36 @@ def bound(tag, value, limit):
     w = BOUNDS.get(tag, (0.0, limit))[0]
     BOUNDS[tag] = (max(w, value), limit)
     assert value < limit, (tag, value, limit)
+
+
+KEEP = []  # device buffers of Out: they stay alive until the test that made them has synchronised (release())
+
+
+class Out:
+    """n output elements on the GPU followed by GUARD sentinel elements (tests/algo_cases.py).  `init` fills the n elements (a buffer a
+    kernel updates in place); otherwise they hold the sentinel too, so that an element the kernel skipped shows."""
+
+    def __init__(self, n, dtype=torch.float32, sentinel=None, init=None):
+        from tests import algo_cases as ac
+        self.n = n
+        self.sentinel = ac.SENTINEL if sentinel is None else sentinel
+        self.full = torch.full((n + ac.GUARD,), self.sentinel, dtype=dtype, device="cuda")
+        if init is not None:
+            self.full[:n] = init.to("cuda")
+        KEEP.append(self.full)
+
+    @property
+    def ptr(self):
+        from bsi_amd import _native
+        return _native.ptr(self.full)
+
+    def get(self):
+        """The output on the CPU, after checking that the kernel wrote nothing behind its last element."""
+        h = self.full.cpu()
+        assert bool((h[self.n:] == self.sentinel).all()), "the kernel wrote past the end of its output"
+        return h[:self.n].clone()
+
+
+def release():
+    torch.cuda.synchronize()
+    KEEP.clear()
