@@ -412,7 +412,8 @@ int bsi_attention_fwd_train(const void* qkv, int ld_qkv, int B, int tokens, int 
 
 // Training attention with the counter-based dropout of the DiT blocks as entry points of their own (the engine calls the two
 // functions above): words = NULL, or the 8 KB per (image, head) of lane-mask words (256 tokens, head dim 64) that the forward writes and
-// the backward reads -- what bsi_dit_train_forward / bsi_dit_backward keep on their tape.
+// the backward reads -- what bsi_dit_train_forward / bsi_dit_backward keep on their tape.  The backward serves head dim 64 and 128 at
+// any multiple of 64 tokens up to 8192; outside 256 tokens x head dim 64 there are no words and `words` must be NULL.
 extern "C" int bsi_attention_fwd_dropout(const void* qkv, int ld_qkv, int B, int tokens, int heads, int dh, void* out, int ld_out, float* lse,
                                          float p, unsigned long long seed, unsigned site, void* words, bsi_stream_t stream) {
     BSI_CHECK_ARG(p >= 0.f && p < 1.f, "bsi_attention_fwd_dropout: dropout probability %g outside [0, 1)", (double)p);
@@ -423,5 +424,6 @@ extern "C" int bsi_attention_bwd_dropout(const void* qkv, int ld_qkv, const void
                                          int tokens, int heads, int dh, void* dqkv, int ld_dqkv, float p, unsigned long long seed, unsigned site,
                                          const void* words, bsi_stream_t stream) {
     BSI_CHECK_ARG(p >= 0.f && p < 1.f, "bsi_attention_bwd_dropout: dropout probability %g outside [0, 1)", (double)p);
-    return bsi_attention_bwd_drop(qkv, ld_qkv, out, dout, ld_o, lse, B, tokens, heads, dh, dqkv, ld_dqkv, make_drop(p, seed, site), stream, words);
+    // head dim 64 at up to 256 tokens: the resident / persistent kernels; head dim 64 above that and head dim 128: the streamed kernel
+    return bsi_attention_bwd_train(qkv, ld_qkv, out, dout, ld_o, lse, B, tokens, heads, dh, dqkv, ld_dqkv, make_drop(p, seed, site), stream, words);
 }

@@ -9,6 +9,12 @@
 //   pass 2: a wave owns 16*JR keys, Q and dO chunks stream:  S = Q.K^T, dP = dO.V^T, dV^T += dO^T . P, dK^T += Q^T . dS.
 // No atomics, deterministic.  One LDS image per tile serves row reads (ds_read_b128) and transposed reads
 // (ds_read_b64_tr_b16): 16-B chunk index ^= swz(row).
+//
+// DROP (head dims 64 and 128, the DiT's training attention): the forward dropped the attention weights with the counter hash,
+// O = P~ . V with P~ = keep ? dc.scale * P : 0.  Then dV += P~^T . dO, dP = keep ? dc.scale * (dO . V^T) : 0 and
+// dS = scale * P * (dP - delta); delta = rowsum(dO * O) is unchanged because O already carries the mask.  The mask is the
+// forward's, keep(row = bh * T + query, column = key); the row hashes of all T queries sit in a third LDS array beside lse and
+// delta, so dropout adds arithmetic and LDS reads but no global-memory access.
 #include "common.h"
 #include "dit_ops.h"
 
@@ -51,11 +57,13 @@ __device__ __forceinline__ s16x4 grow4(const __bf16* p, int g) { return *reinter
 
 #define TR(ptr) __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(ptr))
 
-template <int DH>
+template <int DH, bool DROP>
 __global__ __launch_bounds__(512) void attention_bwd_stream_kernel(const __bf16* __restrict__ qkv, int ld_qkv,
                                                                    const __bf16* __restrict__ o, const __bf16* __restrict__ dout,
                                                                    int ld_o, const float* __restrict__ lse, int T, int heads,
-                                                                   __bf16* __restrict__ dqkv, int ld_dqkv, float scale) {
+                                                                   __bf16* __restrict__ dqkv, int ld_dqkv, float scale,
+                                                                   DropCfg dc /* DROP only */) {
+    static_assert(!DROP || DH == 64 || DH == 128, "dropout instances: head dims 64 and 128");
     constexpr int RB = DH * 2, CPR = DH / 8, KS = DH / 32, DT = DH / 16;
     constexpr int JR = DH <= 64 ? 2 : 1;      // 16-row tiles owned by a wave
     constexpr int NLD = 2 * 64 * CPR;         // 16-B loads per streamed chunk (two tiles)
@@ -67,6 +75,8 @@ __global__ __launch_bounds__(512) void attention_bwd_stream_kernel(const __bf16*
     char* TB = TA + 64 * RB;
     float* lse_s = reinterpret_cast<float*>(TB + 64 * RB);  // [T] lse * log2(e)
     float* dlt_s = lse_s + T;                               // [T] delta = rowsum(dO * O)
+    unsigned* rowh_s = reinterpret_cast<unsigned*>(dlt_s + T);  // [T] drop_row of row bh * T + query (DROP only; not allocated otherwise)
+    const unsigned thr16 = dc.thr >> 16;
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int bh = blockIdx.y, b = bh / heads, h = bh % heads;
@@ -97,6 +107,7 @@ __global__ __launch_bounds__(512) void attention_bwd_stream_kernel(const __bf16*
         if (hlf == 0) {
             dlt_s[r] = a;
             lse_s[r] = lse[(size_t)bh * T + r] * L2E;
+            if constexpr (DROP) rowh_s[r] = drop_row(dc, (unsigned)bh * T + r);
         }
     }
 
@@ -134,6 +145,7 @@ __global__ __launch_bounds__(512) void attention_bwd_stream_kernel(const __bf16*
         bf16x8 qf[JR][KS1], dof[JR][KS1];
         s16x4 qh[JR] = {}, doh[JR] = {};
         float lq[JR], dq_delta[JR];
+        unsigned rh[JR] = {};
 #pragma unroll
         for (int jq = 0; jq < JR; ++jq) {
             const int q = r0c + 16 * jq + c16;
@@ -159,7 +171,11 @@ __global__ __launch_bounds__(512) void attention_bwd_stream_kernel(const __bf16*
             __syncthreads();
             if (kc == 0) {
 #pragma unroll
-                for (int jq = 0; jq < JR; ++jq) { lq[jq] = lse_s[r0c + 16 * jq + c16]; dq_delta[jq] = dlt_s[r0c + 16 * jq + c16]; }
+                for (int jq = 0; jq < JR; ++jq) {
+                    lq[jq] = lse_s[r0c + 16 * jq + c16];
+                    dq_delta[jq] = dlt_s[r0c + 16 * jq + c16];
+                    if constexpr (DROP) rh[jq] = rowh_s[r0c + 16 * jq + c16];
+                }
             }
             if (kc + 64 < T) prefetch(Kg, ld_qkv, Vg, ld_qkv, kc + 64);
             f32x4 s[4][JR], dp[4][JR];
@@ -190,12 +206,18 @@ __global__ __launch_bounds__(512) void attention_bwd_stream_kernel(const __bf16*
 #pragma unroll
             for (int kt = 0; kt < 4; ++kt)
 #pragma unroll
-                for (int jq = 0; jq < JR; ++jq)
+                for (int jq = 0; jq < JR; ++jq) {
+                    // a lane's four rows are keys kc + 16kt + 4g + r of one query: one aligned quad of mask columns, one hash
+                    DropQuad mq = {};
+                    if constexpr (DROP) mq = drop_quad(rh[jq], (unsigned)(kc >> 2) + 4 * kt + g);
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         const float pv = __builtin_amdgcn_exp2f(__fmaf_rn(s[kt][jq][r], sl2, -lq[jq]));
-                        s[kt][jq][r] = scale * pv * (dp[kt][jq][r] - dq_delta[jq]);
+                        float dpv = dp[kt][jq][r];
+                        if constexpr (DROP) dpv = drop_field(mq, (unsigned)r) >= thr16 ? dpv * dc.scale : 0.0f;
+                        s[kt][jq][r] = scale * pv * (dpv - dq_delta[jq]);
                     }
+                }
 #pragma unroll
             for (int kb = 0; kb < 2; ++kb) {
                 bf16x8 dsf[JR];
@@ -291,13 +313,27 @@ __global__ __launch_bounds__(512) void attention_bwd_stream_kernel(const __bf16*
             for (int qt = 0; qt < 4; ++qt) {
                 const f32x4 lr = *reinterpret_cast<const f32x4*>(lse_s + qc + 16 * qt + 4 * g);
                 const f32x4 dr = *reinterpret_cast<const f32x4*>(dlt_s + qc + 16 * qt + 4 * g);
+                u32x4 rq = {};
+                if constexpr (DROP) rq = *reinterpret_cast<const u32x4*>(rowh_s + qc + 16 * qt + 4 * g);
 #pragma unroll
                 for (int jk = 0; jk < JR; ++jk)
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         const float pv = __builtin_amdgcn_exp2f(__fmaf_rn(s[qt][jk][r], sl2, -lr[r]));
-                        s[qt][jk][r] = pv;                                        // P (for dV)
-                        dp[qt][jk][r] = scale * pv * (dp[qt][jk][r] - dr[r]);     // dS
+                        if constexpr (DROP) {
+                            // four queries against one key: a quad hash per element, the row hashes come from the prologue.
+                            // The key's 16-bit field of the hash pair is picked with a lane mask and a shift: drop_field's select
+                            // on a lane-dependent column became an indexed read of a stack copy of the pair (scratch).
+                            const unsigned col = (unsigned)(r0c + 16 * jk + c16);
+                            const DropQuad mq = drop_quad(rq[r], col >> 2);
+                            const unsigned hw = mq.h1 ^ ((mq.h1 ^ mq.h2) & (0u - ((col >> 1) & 1u)));
+                            const bool keep = ((hw >> (16 * (col & 1u))) & 0xffffu) >= thr16;
+                            s[qt][jk][r] = keep ? pv * dc.scale : 0.0f;           // dropped P (for dV)
+                            dp[qt][jk][r] = scale * pv * ((keep ? dp[qt][jk][r] * dc.scale : 0.0f) - dr[r]);
+                        } else {
+                            s[qt][jk][r] = pv;                                        // P (for dV)
+                            dp[qt][jk][r] = scale * pv * (dp[qt][jk][r] - dr[r]);     // dS
+                        }
                     }
             }
 #pragma unroll
@@ -348,26 +384,32 @@ __global__ __launch_bounds__(512) void attention_bwd_stream_kernel(const __bf16*
 }
 #undef TR
 
-template <int DH>
+template <int DH, bool DROP>
 int launch_stream(const __bf16* qkv, int ld_qkv, const __bf16* o, const __bf16* dout, int ld_o, const float* lse, int B, int T,
-                  int heads, __bf16* dqkv, int ld_dqkv, hipStream_t s) {
+                  int heads, __bf16* dqkv, int ld_dqkv, DropCfg dc, hipStream_t s) {
     constexpr int JR = DH <= 64 ? 2 : 1;
-    const size_t lds = (size_t)2 * 64 * DH * 2 + (size_t)2 * T * sizeof(float);
-    auto kern = attention_bwd_stream_kernel<DH>;
+    // two streamed tiles, lse and delta of every query, and with dropout their row hashes
+    const size_t lds = (size_t)2 * 64 * DH * 2 + (size_t)(DROP ? 3 : 2) * T * sizeof(float);
+    int dev = 0, lds_max = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess)
+        lds_max = 0;
+    BSI_CHECK_ARG(lds <= (size_t)lds_max, "bsi_attention_bwd_long: tokens=%d at head dim %d needs %zu bytes of LDS, the device has %d", T, DH,
+                  lds, lds_max);
+    auto kern = attention_bwd_stream_kernel<DH, DROP>;
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     dim3 grid((T + 128 * JR - 1) / (128 * JR), B * heads);
     hipLaunchKernelGGL(kern, grid, dim3(512), lds, s, qkv, ld_qkv, o, dout, ld_o, lse, T, heads, dqkv, ld_dqkv,
-                       1.0f / sqrtf((float)DH));
+                       1.0f / sqrtf((float)DH), dc);
     BSI_CHECK_LAUNCH("bsi_attention_bwd_long");
     return BSI_OK;
 }
 
-}  // namespace
-
-extern "C" int bsi_attention_bwd_long(const void* qkv, int ld_qkv, const void* out, const void* dout, int ld_o, const float* lse,
-                                      int B, int tokens, int heads, int dh, void* dqkv, int ld_dqkv, bsi_stream_t stream) {
+// head dims 16 .. 128 without dropout; 64 and 128 with it (dc.thr != 0)
+int stream_impl(const void* qkv, int ld_qkv, const void* out, const void* dout, int ld_o, const float* lse, int B, int tokens, int heads,
+                int dh, void* dqkv, int ld_dqkv, DropCfg dc, bsi_stream_t stream) {
     BSI_CHECK_ARG(qkv && out && dout && lse && dqkv && B > 0 && heads > 0, "bsi_attention_bwd_long: bad args");
     BSI_CHECK_ARG(dh == 16 || dh == 32 || dh == 64 || dh == 128, "bsi_attention_bwd_long: head dim %d unsupported (16, 32, 64 or 128)", dh);
+    BSI_CHECK_ARG(!dc.thr || dh == 64 || dh == 128, "bsi_attention_bwd_long: head dim %d has no dropout instance (64 or 128)", dh);
     BSI_CHECK_ARG(tokens > 0 && tokens % 64 == 0 && tokens <= 8192, "bsi_attention_bwd_long: tokens=%d must be a multiple of 64, <= 8192",
                   tokens);
     BSI_CHECK_ARG(ld_qkv % 8 == 0 && ld_o % 8 == 0 && ld_dqkv % 4 == 0, "bsi_attention_bwd_long: bad leading dimensions");
@@ -376,8 +418,34 @@ extern "C" int bsi_attention_bwd_long(const void* qkv, int ld_qkv, const void* o
     const __bf16* o = reinterpret_cast<const __bf16*>(out);
     const __bf16* d = reinterpret_cast<const __bf16*>(dout);
     __bf16* dq = reinterpret_cast<__bf16*>(dqkv);
-    if (dh == 16) return launch_stream<16>(q, ld_qkv, o, d, ld_o, lse, B, tokens, heads, dq, ld_dqkv, s);
-    if (dh == 32) return launch_stream<32>(q, ld_qkv, o, d, ld_o, lse, B, tokens, heads, dq, ld_dqkv, s);
-    if (dh == 64) return launch_stream<64>(q, ld_qkv, o, d, ld_o, lse, B, tokens, heads, dq, ld_dqkv, s);
-    return launch_stream<128>(q, ld_qkv, o, d, ld_o, lse, B, tokens, heads, dq, ld_dqkv, s);
+    if (dc.thr) {
+        if (dh == 64) return launch_stream<64, true>(q, ld_qkv, o, d, ld_o, lse, B, tokens, heads, dq, ld_dqkv, dc, s);
+        return launch_stream<128, true>(q, ld_qkv, o, d, ld_o, lse, B, tokens, heads, dq, ld_dqkv, dc, s);
+    }
+    if (dh == 16) return launch_stream<16, false>(q, ld_qkv, o, d, ld_o, lse, B, tokens, heads, dq, ld_dqkv, DropCfg{}, s);
+    if (dh == 32) return launch_stream<32, false>(q, ld_qkv, o, d, ld_o, lse, B, tokens, heads, dq, ld_dqkv, DropCfg{}, s);
+    if (dh == 64) return launch_stream<64, false>(q, ld_qkv, o, d, ld_o, lse, B, tokens, heads, dq, ld_dqkv, DropCfg{}, s);
+    return launch_stream<128, false>(q, ld_qkv, o, d, ld_o, lse, B, tokens, heads, dq, ld_dqkv, DropCfg{}, s);
+}
+
+}  // namespace
+
+extern "C" int bsi_attention_bwd_long(const void* qkv, int ld_qkv, const void* out, const void* dout, int ld_o, const float* lse,
+                                      int B, int tokens, int heads, int dh, void* dqkv, int ld_dqkv, bsi_stream_t stream) {
+    return stream_impl(qkv, ld_qkv, out, dout, ld_o, lse, B, tokens, heads, dh, dqkv, ld_dqkv, DropCfg{}, stream);
+}
+
+// The training attention backward of the DiT engine and of bsi_attention_bwd_dropout.  Head dim 64 at up to 256 tokens stays with
+// the resident / persistent kernels of attention_bwd.hip (arguments unchanged); head dim 64 above 256 tokens and head dim 128 take
+// the streamed kernel above, with its dropout instance when dc.thr != 0.  The streamed kernel reads no mask words and writes no
+// bias rows (bsi_attention_bwd_emits_bias answers false for it).
+int bsi_attention_bwd_train(const void* qkv, int ld_qkv, const void* out, const void* dout, int ld_o, const float* lse, int B,
+                            int tokens, int heads, int dh, void* dqkv, int ld_dqkv, DropCfg dc, bsi_stream_t stream, const void* maskw,
+                            float* bias_rows) {
+    BSI_CHECK_ARG(dh == 64 || dh == 128, "bsi_attention_bwd: head dim %d unsupported (64 or 128)", dh);
+    if (dh == 64 && tokens <= 256)
+        return bsi_attention_bwd_drop(qkv, ld_qkv, out, dout, ld_o, lse, B, tokens, heads, dh, dqkv, ld_dqkv, dc, stream, maskw, bias_rows);
+    BSI_CHECK_ARG(!maskw, "bsi_attention_bwd: mask words exist at 256 tokens and head dim 64 only (tokens=%d, head dim %d)", tokens, dh);
+    BSI_CHECK_ARG(!bias_rows, "bsi_attention_bwd: bias rows are an output of the single-sweep kernel only");
+    return stream_impl(qkv, ld_qkv, out, dout, ld_o, lse, B, tokens, heads, dh, dqkv, ld_dqkv, dc, stream);
 }

@@ -34,6 +34,12 @@ int bsi_attention_fwd_train(const void* qkv, int ld_qkv, int B, int tokens, int 
 int bsi_attention_bwd_drop(const void* qkv, int ld_qkv, const void* out, const void* dout, int ld_o, const float* lse,
                            int B, int tokens, int heads, int dh, void* dqkv, int ld_dqkv, DropCfg dc, bsi_stream_t stream,
                            const void* maskw = nullptr, float* bias_rows = nullptr);
+// attention_bwd_stream.hip: the training backward of the DiT.  Head dim 64 at up to 256 tokens: bsi_attention_bwd_drop, arguments
+// unchanged.  Head dim 64 above 256 tokens and head dim 128 (multiples of 64 tokens up to 8192): the streamed kernel, with its
+// dropout instance when dc.thr != 0; maskw and bias_rows must be null there (bsi_attention_bwd_emits_bias answers false).
+int bsi_attention_bwd_train(const void* qkv, int ld_qkv, const void* out, const void* dout, int ld_o, const float* lse, int B,
+                            int tokens, int heads, int dh, void* dqkv, int ld_dqkv, DropCfg dc, bsi_stream_t stream,
+                            const void* maskw = nullptr, float* bias_rows = nullptr);
 // gemm_bf16.hip: can the MUL_GELUGRAD GEMM of this shape write bsi_gemm_args::colsum_rows?
 bool bsi_gemm_emits_colsum(int M, int K);
 // gemm_bf16.hip: the kernel / split-K plan of a plain bf16 epilogue through bsi_gemm_bf16_ws on `cus` compute units

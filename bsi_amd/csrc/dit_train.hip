@@ -64,7 +64,14 @@ struct Tape {
 // kernels consume them (bsi_attention_uses_mask_words: 256 tokens, head dim 64); elsewhere the region is empty and BlockTape::maskw
 // is NULL, so no kernel can read words that were never written (forward and backward carve the tape with this one function).
 inline size_t mask_words_bytes(const Dims& d, int B) {
-    return bsi_attention_uses_mask_words(d.tokens, 64) ? au((size_t)B * d.heads * 8192) : 0;
+    return bsi_attention_uses_mask_words(d.tokens, d.heads > 0 ? d.dim / d.heads : 0) ? au((size_t)B * d.heads * 8192) : 0;
+}
+
+// What the training engine runs: heads of 64 or 128 channels, a multiple of 64 tokens up to 1024 (head dim 64 at up to 256 tokens
+// on the resident / persistent attention backward, everything else on the streamed one: bsi_attention_bwd_train), dim <= 1024.
+inline bool train_geometry_ok(const Dims& d) {
+    const int dh = d.heads > 0 && d.dim % d.heads == 0 ? d.dim / d.heads : 0;
+    return d.tokens > 0 && d.tokens % 64 == 0 && d.tokens <= 1024 && d.dim % 64 == 0 && (dh == 64 || dh == 128) && d.dim <= 1024;
 }
 
 inline Tape carve_tape(const Dims& d, int B, void* base) {
@@ -246,9 +253,9 @@ extern "C" int bsi_dit_train_forward(const bsi_dit_config* cfg, const bsi_dit_we
                   "bsi_dit_train_forward: c_in/c_skip/c_out must be given together");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const Dims d = dims_of(cfg, B);
-    BSI_CHECK_ARG(d.tokens % 64 == 0 && d.dim % 64 == 0 && d.dim / d.heads == 64 && d.tokens <= 256 && d.dim <= 1024,
-                  "bsi_dit_train_forward: unsupported geometry (tokens %d, dim %d, head dim %d)", d.tokens, d.dim, d.dim / d.heads);
-    const int dim = d.dim, M = (int)d.M;
+    BSI_CHECK_ARG(train_geometry_ok(d), "bsi_dit_train_forward: unsupported geometry (tokens %d, dim %d, head dim %d)", d.tokens, d.dim,
+                  d.heads > 0 ? d.dim / d.heads : 0);
+    const int dim = d.dim, M = (int)d.M, dh = d.dim / d.heads;
     const int mod_stride = d.depth * 6 * dim;
     Tape tp = carve_tape(d, B, tape_mem);
 
@@ -329,12 +336,12 @@ extern "C" int bsi_dit_train_forward(const bsi_dit_config* cfg, const bsi_dit_we
         // (with dropout on the DiT geometry, this HBM-bound pass also computes the attention layer's dropout-mask words: row m ->
         //  block m, M = B * tokens = B * heads * 16 blocks when tokens == 16 * heads)
         const DropCfg adc = make_drop(dropout_p, seed, 2 * l);
-        const bool ride = adc.thr != 0 && bsi_attention_uses_mask_words(d.tokens, 64) && d.tokens == 16 * d.heads && dim > 256 && dim <= 1024;
+        const bool ride = adc.thr != 0 && bsi_attention_uses_mask_words(d.tokens, dh) && d.tokens == 16 * d.heads && dim > 256 && dim <= 1024;
         TRY(bsi_resid_ln_modulate_drop(l == 0 ? bt.xa : x_prev, M, dim, 1e-5f, pend_delta, pend_gate, ml, ml + dim, B, mod_stride,
                                        d.tokens, nullptr, nullptr, bt.xn1, DropCfg{}, stream, bt.xa, bt.sa, nullptr, nullptr, 1,
                                        ride ? adc : DropCfg{}, ride ? bt.maskw : nullptr));
         TRY(gemm(bt.xn1, dim, bw.qkv_w, dim, bw.qkv_b, bt.qkv, 3 * dim, M, 3 * dim, dim, BSI_EPI_BIAS_BF16, nullptr, nullptr, nullptr, 0, stream));
-        TRY(bsi_attention_fwd_train(bt.qkv, 3 * dim, B, d.tokens, d.heads, 64, bt.ao, dim, bt.lse,
+        TRY(bsi_attention_fwd_train(bt.qkv, 3 * dim, B, d.tokens, d.heads, dh, bt.ao, dim, bt.lse,
                                     adc, stream, bt.maskw, ride));
         TRY(gemm(bt.ao, dim, bw.out_w, dim, bw.out_b, bt.d1, dim, M, dim, dim, BSI_EPI_BIAS_BF16, nullptr, nullptr, nullptr, 0, stream));
         TRY(bsi_resid_ln_modulate_drop(bt.xa, M, dim, 1e-5f, bt.d1, ml + 2 * dim, ml + 3 * dim, ml + 4 * dim, B, mod_stride,
@@ -362,7 +369,9 @@ extern "C" int bsi_dit_backward(const bsi_dit_config* cfg, const bsi_dit_weights
     BSI_CHECK_ARG(dropout_p >= 0.f && dropout_p < 1.f, "bsi_dit_backward: dropout probability %g outside [0, 1)", (double)dropout_p);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const Dims d = dims_of(cfg, B);
-    const int dim = d.dim, M = (int)d.M;
+    BSI_CHECK_ARG(train_geometry_ok(d), "bsi_dit_backward: unsupported geometry (tokens %d, dim %d, head dim %d)", d.tokens, d.dim,
+                  d.heads > 0 ? d.dim / d.heads : 0);
+    const int dim = d.dim, M = (int)d.M, dh = d.dim / d.heads;
     const int mod_stride = d.depth * 6 * dim;
     Tape tp = carve_tape(d, B, tape_mem);
     BwdWs ws = carve_bwd(d, B, workspace);
@@ -370,7 +379,6 @@ extern "C" int bsi_dit_backward(const bsi_dit_config* cfg, const bsi_dit_weights
     // modulation gradients: every 64-token slab of an image stores its sums into its own plane (bsi_ln_gate_bwd_drop with a plane
     // stride), the planes are added in fixed order when the block's adaLN backward needs them: no atomics, no zero fill, bit
     // reproducible.  Two blocks are in flight at a time (the fused kernel of block l also writes g_m of block l - 1): parity slots.
-    BSI_CHECK_ARG(d.tokens % 64 == 0, "bsi_dit_backward: tokens=%d must be a multiple of 64", d.tokens);
     const int nplanes = d.tokens / 64;
     const size_t plane = (size_t)B * 6 * dim;  // floats per plane
     const int dstride = 6 * dim;               // row stride inside a plane
@@ -384,7 +392,7 @@ extern "C" int bsi_dit_backward(const bsi_dit_config* cfg, const bsi_dit_weights
     const bool rel_fc1 = !fused_bias && bsi_gemm_emits_colsum(M, dim);
     const int r64 = M / 64, r128 = (M + 127) / 128;
     auto rel_qkv_of = [&](int l) {  // depends on the block only through its dropout site (on or off for all)
-        return !fused_bias && bsi_attention_bwd_emits_bias(d.tokens, 64, make_drop(dropout_p, seed, 2 * l), block_tape(tp, d, B, l).maskw);
+        return !fused_bias && bsi_attention_bwd_emits_bias(d.tokens, dh, make_drop(dropout_p, seed, 2 * l), block_tape(tp, d, B, l).maskw);
     };
     // decoder: dX = d/dx_final, parameter gradients of patch_decoder (dit.py:163-165)
     {
@@ -438,8 +446,8 @@ extern "C" int bsi_dit_backward(const bsi_dit_config* cfg, const bsi_dit_weights
         if (pair) {}
         else if (rel_dd) TRY(bsi_gemm_tn_bf16(ws.dd, dim, bt.ao, dim, M, dim, dim, bg.out_w, dim, 0, ws.tn, stream));
         else TRY(bsi_gemm_tn_bias_bf16(ws.dd, dim, bt.ao, dim, M, dim, dim, bg.out_w, dim, bg.out_b, 0, ws.tn, stream));
-        TRY(bsi_attention_bwd_drop(bt.qkv, 3 * dim, bt.ao, ws.dsmall, dim, bt.lse, B, d.tokens, d.heads, 64, ws.dbig, 3 * dim,
-                                   make_drop(dropout_p, seed, 2 * l), stream, bt.maskw, rel_qkv ? ws.rows_qkv : nullptr));
+        TRY(bsi_attention_bwd_train(bt.qkv, 3 * dim, bt.ao, ws.dsmall, dim, bt.lse, B, d.tokens, d.heads, dh, ws.dbig, 3 * dim,
+                                    make_drop(dropout_p, seed, 2 * l), stream, bt.maskw, rel_qkv ? ws.rows_qkv : nullptr));
         if (rel_dd || rel_fc1 || rel_qkv) {  // the slab tables of this block are complete (rows_fc2 is rewritten by the LayerNorm-1 launch below)
             bsi_colsum_job jobs[4];
             int nj = 0;

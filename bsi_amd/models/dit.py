@@ -105,7 +105,12 @@ class DiT(nn.Module):
 
 
 class DenoisingDiT(nn.Module):
-    """Diffusion Transformer denoiser f(mu, t) — same constructor as bsi.models.dit.DenoisingDiT."""
+    """Diffusion Transformer denoiser f(mu, t) — same constructor as bsi.models.dit.DenoisingDiT.
+
+    Any `heads` builds, as in the reference; the kernels decide at first use.  Sampling and ELBO run head dims (dim / heads) 64 and
+    128 at any multiple of 64 tokens; training runs the same head dims at up to 1024 tokens, dim <= 1024, with or without dropout
+    (e.g. the paper's CIFAR-10 model: dim 128, one head, patch 2).  Other geometries raise a RuntimeError naming tokens, dim and
+    head dim."""
 
     def __init__(self, data_shape, patch_size: int, dim: int, depth: int, heads: int, dropout: float | None = None,
                  fourier_features: FourierFeatures | None = None, **kwargs):

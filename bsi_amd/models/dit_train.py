@@ -2,6 +2,10 @@
 memory (`bsi_dit_train_forward`) and whose backward is the hand-written HIP backward (`bsi_dit_backward`).
 torch's autograd only carries the parameter gradients out; no torch op computes anything.
 
+Geometries: heads of 64 or 128 channels, a multiple of 64 tokens up to 1024, dim <= 1024.  Heads of 64 channels at up to 256 tokens
+use the resident / persistent attention backward, everything else the streamed one (with the same counter-based dropout mask);
+both engine entry points refuse anything else with a message naming tokens, dim and head dim.
+
 Replaces autograd over bsi/models/dit.py:87-103,174-181 of the reference inside
 `BSI.train_loss(...).mean().backward()` (bsi/tasks/bsi.py:187-194)."""
 import ctypes as C

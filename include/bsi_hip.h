@@ -313,7 +313,8 @@ int bsi_attention_bwd(const void* qkv, int ld_qkv, const void* out, const void* 
                       int B, int tokens, int heads, int dh, void* dqkv, int ld_dqkv, bsi_stream_t stream);
 /* Same contract for long sequences / wide heads (UNet centre attention, attention.py:18,38: 1024 positions, dh 128):
  * the other side of each pass is streamed through LDS; tokens % 64 == 0, dh 16, 32, 64 or 128 (32: the per-block attention of
- * residual_block.py:50-64; 16 and 32: the centre attention with n_attention_heads 8 and 4 at dim 128), no dropout. */
+ * residual_block.py:50-64; 16 and 32: the centre attention with n_attention_heads 8 and 4 at dim 128), no dropout (the DiT's
+ * attention-weight dropout on this kernel: bsi_attention_bwd_dropout). */
 int bsi_attention_bwd_long(const void* qkv, int ld_qkv, const void* out, const void* dout, int ld_o, const float* lse,
                            int B, int tokens, int heads, int dh, void* dqkv, int ld_dqkv, bsi_stream_t stream);
 
@@ -666,7 +667,8 @@ typedef struct bsi_dit_grads {
 size_t bsi_dit_tape_bytes(const bsi_dit_config* cfg, int B);
 size_t bsi_dit_backward_workspace_bytes(const bsi_dit_config* cfg, int B);
 /* out = c_skip*mu + c_out*f(c_in*mu, t) (or f(mu, t) with NULL coefficients), per-sample t/coefficients [B];
- * records the activations the backward needs in `tape` (bsi_dit_tape_bytes). */
+ * records the activations the backward needs in `tape` (bsi_dit_tape_bytes).  Geometries: dim / heads 64 or 128, tokens % 64 == 0
+ * up to 1024, dim <= 1024; bsi_dit_backward refuses the same others. */
 int bsi_dit_train_forward(const bsi_dit_config* cfg, const bsi_dit_weights* w /*host*/, int B, const float* mu,
                           const float* t, const float* c_in, const float* c_skip, const float* c_out, float* out,
                           void* tape, float dropout_p, unsigned long long seed, bsi_stream_t stream);
@@ -691,7 +693,9 @@ int bsi_attention_dropout_words(float p, unsigned long long seed, unsigned site,
  * (b * heads + h) * tokens + query, col = key).  words: NULL (both sides evaluate the hash), or -- 256 tokens, head dim 64 only -- a
  * buffer of 8 KB per (image, head) that the forward FILLS with the lane-mask words and the backward READS (what the training engine
  * keeps on its tape); pass the same value to both.  lse as bsi_attention_fwd_lse.  p = 0 is plain attention.  Forward: dh 32, 64 or 128
- * (head dim 16 is refused: it has no dropout instance); backward: dh 64, tokens <= 256. */
+ * (head dim 16 is refused: it has no dropout instance); backward: dh 64 or 128, tokens % 64 == 0 up to 8192 (dh 64 at up to 256
+ * tokens on the kernels of bsi_attention_bwd, everything else on the streamed kernel of bsi_attention_bwd_long with the same mask;
+ * there `words` must be NULL).  Head dims 16, 32 and others are refused with the value in the message, before anything is written. */
 int bsi_attention_fwd_dropout(const void* qkv, int ld_qkv, int B, int tokens, int heads, int dh, void* out, int ld_out, float* lse,
                               float p, unsigned long long seed, unsigned site, void* words, bsi_stream_t stream);
 int bsi_attention_bwd_dropout(const void* qkv, int ld_qkv, const void* out, const void* dout, int ld_o, const float* lse, int B,
