@@ -452,8 +452,8 @@ __global__ __launch_bounds__(TPB) void ln_gate_bwd_kernel(
 //   dX = LN_bwd(dy * lnw)     (dX is WRITTEN, it starts the residual gradient)
 // The decoder weight gradient dWdec = dY^T y is a token-contraction and goes to the TN GEMM: this kernel writes its
 // operands yb = bf16(y) [M, d] and dYb = bf16(dY) [M, Pp] (Pp = P rounded up to 8, zero padded).
-// dlnw / dlnb / dbdec: per-wave register accumulators over the wave's rows, one LDS reduction per workgroup, one
-// global atomic per element per workgroup.
+// dlnw / dlnb / dbdec: per-wave register accumulators over the wave's rows, one LDS reduction per workgroup, one slab of
+// `parts` per workgroup (summed in slab order by the launcher: no atomics).  This kernel: P <= 64, lane o holds dY[o].
 template <int VPL, bool WLDS>
 __global__ void dit_final_bwd_kernel(const float* __restrict__ x, int Mtok, int d, int P, int Pp,
                                      const float* __restrict__ ln_w, const float* __restrict__ ln_b,
@@ -592,6 +592,166 @@ __global__ void dit_final_bwd_kernel(const float* __restrict__ x, int Mtok, int 
     }
     float* slab = parts + (size_t)blockIdx.x * (2 * (size_t)d + 64);
     for (int i = threadIdx.x; i < 2 * d + 64; i += blockDim.x) slab[i] = gsm[i];
+}
+
+// The same kernel for 64 < P <= 256: a lane carries NPL = ceil(P / 64) decoder columns -- lane L holds dY[j * 64 + L], j < NPL, in
+// dy_o[j], sums them in db_acc[j] and stores them to dYb; the bias-sum region behind the two LayerNorm rows in LDS and in a slab of
+// `parts` is [64 NPL].  dy accumulates over o = 0 .. P - 1 in index order as above.  (A template of its own so that the P <= 64
+// instances above stay instruction for instruction what they were.)
+template <int VPL, bool WLDS, int NPL>
+__global__ __launch_bounds__(TPB) void dit_final_bwd_wide_kernel(const float* __restrict__ x, int Mtok, int d, int P, int Pp,
+                                                                  const float* __restrict__ ln_w, const float* __restrict__ ln_b,
+                                                                  const float* __restrict__ dec_w, int C, int H, int W, int ps,
+                                                                  const float* __restrict__ g_xhat, const float* __restrict__ c_out,
+                                                                  int coef_stride, float* __restrict__ dX, __bf16* __restrict__ yb,
+                                                                  __bf16* __restrict__ dYb, float* __restrict__ parts) {
+    static_assert(NPL >= 2 && NPL <= 4, "one to four decoder columns per lane; one is dit_final_bwd_kernel");
+    extern __shared__ __attribute__((aligned(16))) float sm[];  // [2][d] + [64 NPL] reduction, then (WLDS) [P][d] weights
+    float* gsm = sm;
+    float* wsm = sm + 2 * (size_t)d + 64 * NPL;
+    const int d4 = d >> 2;
+    for (int i = threadIdx.x; i < 2 * d4; i += blockDim.x) reinterpret_cast<f32x4*>(gsm)[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+    if constexpr (WLDS)
+        for (int i = threadIdx.x; i < P * d4; i += blockDim.x)
+            reinterpret_cast<f32x4*>(wsm)[i] = reinterpret_cast<const f32x4*>(dec_w)[i];
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wpb = blockDim.x >> 6;
+    const int nw = W / ps, tokens = (H / ps) * nw, HW = H * W;
+    float db_acc[NPL];  // lane o accumulates d_dec_b[j * 64 + o]
+#pragma unroll
+    for (int j = 0; j < NPL; ++j) db_acc[j] = 0.f;
+    f32x4 glw[VPL], glb[VPL], lw[VPL], lb[VPL];
+#pragma unroll
+    for (int i = 0; i < VPL; ++i) {
+        const int c = i * 64 + lane;
+        glw[i] = glb[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+        lw[i] = (c < d4) ? reinterpret_cast<const f32x4*>(ln_w)[c] : f32x4{0.f, 0.f, 0.f, 0.f};
+        lb[i] = (c < d4) ? reinterpret_cast<const f32x4*>(ln_b)[c] : f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    for (int row = blockIdx.x * wpb + (threadIdx.x >> 6); row < Mtok; row += gridDim.x * wpb) {
+        const int b_idx = row / tokens, tok = row % tokens;
+        const int th = tok / nw, tw = tok % nw;
+        float dy_o[NPL];  // lane o holds dY[j * 64 + o]
+#pragma unroll
+        for (int j = 0; j < NPL; ++j) {
+            const int o = j * 64 + lane;
+            dy_o[j] = 0.f;
+            if (o < P) {
+                const int intra = o / C, ch = o % C;
+                const int hh = th * ps + intra / ps, ww = tw * ps + intra % ps;
+                dy_o[j] = g_xhat[((size_t)b_idx * C + ch) * HW + (size_t)hh * W + ww];
+                if (c_out) dy_o[j] *= c_out[(size_t)b_idx * coef_stride];
+                db_acc[j] += dy_o[j];
+            }
+            if (o < Pp) dYb[(size_t)row * Pp + o] = (__bf16)dy_o[j];
+        }
+        f32x4 v[VPL];
+        float s = 0.f;
+#pragma unroll
+        for (int i = 0; i < VPL; ++i) {
+            const int c = i * 64 + lane;
+            v[i] = (c < d4) ? reinterpret_cast<const f32x4*>(x + (size_t)row * d)[c] : f32x4{0.f, 0.f, 0.f, 0.f};
+            s += (v[i][0] + v[i][1]) + (v[i][2] + v[i][3]);
+        }
+        const float mean = wave_sum(s) / (float)d;
+        float q = 0.f;
+#pragma unroll
+        for (int i = 0; i < VPL; ++i) {
+            const int c = i * 64 + lane;
+            if (c < d4) {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const float dd = v[i][k] - mean;
+                    q = __fmaf_rn(dd, dd, q);
+                }
+            }
+        }
+        const float rstd = 1.0f / sqrtf(wave_sum(q) / (float)d + 1e-5f);
+        f32x4 dy[VPL];
+#pragma unroll
+        for (int i = 0; i < VPL; ++i) {
+            const int c = i * 64 + lane;
+            dy[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int k = 0; k < 4; ++k) v[i][k] = (v[i][k] - mean) * rstd;  // n
+            if (c < d4) {
+                u32x2 pk;
+                pk[0] = pack_bf16x2(__fmaf_rn(v[i][0], lw[i][0], lb[i][0]), __fmaf_rn(v[i][1], lw[i][1], lb[i][1]));
+                pk[1] = pack_bf16x2(__fmaf_rn(v[i][2], lw[i][2], lb[i][2]), __fmaf_rn(v[i][3], lw[i][3], lb[i][3]));
+                reinterpret_cast<u32x2*>(yb + (size_t)row * d)[c] = pk;
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < NPL; ++j) {
+            const int oe = P < j * 64 + 64 ? P : j * 64 + 64;
+            for (int o = j * 64; o < oe; ++o) {
+                const float g = __shfl(dy_o[j], o - j * 64, 64);
+#pragma unroll
+                for (int i = 0; i < VPL; ++i) {
+                    const int c = i * 64 + lane;
+                    if (c < d4) {
+                        const f32x4 wv = WLDS ? reinterpret_cast<const f32x4*>(wsm + (size_t)o * d)[c]
+                                              : reinterpret_cast<const f32x4*>(dec_w + (size_t)o * d)[c];
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) dy[i][k] = __fmaf_rn(g, wv[k], dy[i][k]);
+                    }
+                }
+            }
+        }
+        float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+        for (int i = 0; i < VPL; ++i) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                glw[i][k] = __fmaf_rn(dy[i][k], v[i][k], glw[i][k]);
+                glb[i][k] += dy[i][k];
+                const float dn = dy[i][k] * lw[i][k];
+                dy[i][k] = dn;
+                s1 += dn;
+                s2 = __fmaf_rn(dn, v[i][k], s2);
+            }
+        }
+        const float m1 = wave_sum(s1) / (float)d, m2 = wave_sum(s2) / (float)d;
+#pragma unroll
+        for (int i = 0; i < VPL; ++i) {
+            const int c = i * 64 + lane;
+            if (c < d4) {
+                f32x4 o;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) o[k] = rstd * (dy[i][k] - m1 - v[i][k] * m2);
+                reinterpret_cast<f32x4*>(dX + (size_t)row * d)[c] = o;
+            }
+        }
+    }
+    // waves add their sums to the block's in wave order (one barrier each: once per block, and the order is fixed), the block
+    // stores them as slab blockIdx.x of `parts` = [gridDim.x][2 d + 64 NPL]; bsi_dit_final_bwd_launch sums the slabs in index order.
+    // No atomics: the three gradients are bit reproducible.
+    float* dbs = gsm + 2 * (size_t)d;  // [64 NPL] decoder bias sums: behind the two LayerNorm rows (the launcher sizes the region)
+    if (threadIdx.x < 64)
+#pragma unroll
+        for (int j = 0; j < NPL; ++j) dbs[j * 64 + threadIdx.x] = 0.f;
+    __syncthreads();
+    for (int w = 0; w < wpb; ++w) {
+        if ((int)(threadIdx.x >> 6) == w) {
+#pragma unroll
+            for (int i = 0; i < VPL; ++i) {
+                const int c = i * 64 + lane;
+                if (c < d4) {
+                    f32x4 a = reinterpret_cast<f32x4*>(gsm)[c], b2 = reinterpret_cast<f32x4*>(gsm + d)[c];
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) { a[k] += glw[i][k]; b2[k] += glb[i][k]; }
+                    reinterpret_cast<f32x4*>(gsm)[c] = a;
+                    reinterpret_cast<f32x4*>(gsm + d)[c] = b2;
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < NPL; ++j)
+                if (j * 64 + lane < P) dbs[j * 64 + lane] += db_acc[j];
+        }
+        __syncthreads();
+    }
+    float* slab = parts + (size_t)blockIdx.x * (2 * (size_t)d + 64 * NPL);
+    for (int i = threadIdx.x; i < 2 * d + 64 * NPL; i += blockDim.x) slab[i] = gsm[i];
 }
 
 // out_bf16 = in_f32 elementwise (optionally * silu'(pre) with pre fp32): used for the adaLN MLP backward
@@ -831,40 +991,53 @@ int bsi_dit_final_bwd_launch(const float* x, int Mtok, int d, int P, const float
                              const float* dec_w, int C, int H, int W, int ps, const float* g_xhat, const float* c_out,
                              int coef_stride, float* dX, void* yb, void* dYb, float* d_dec_b, float* d_ln_w,
                              float* d_ln_b, float* parts, hipStream_t s) {
-    // parts: bsi_dit_final_bwd_parts_floats(Mtok, d) floats of scratch; d_dec_b / d_ln_w / d_ln_b are WRITTEN (not accumulated)
+    // parts: bsi_dit_final_bwd_parts_floats(Mtok, d, P) floats of scratch; d_dec_b / d_ln_w / d_ln_b are WRITTEN (not accumulated)
+    // dYb: [Mtok][Pp] bf16 with Pp = P rounded up to 8
     if (!parts) {
         bsi_set_error("bsi_dit_final_bwd: scratch for the per-block sums missing");
         return BSI_EINVAL;
     }
-    if (P > 64) {
-        bsi_set_error("bsi_dit_final_bwd: decoder P=%d unsupported (needs patch*patch*C <= 64)", P);
+    if (P < 1 || P > BSI_DIT_MAX_P) {
+        bsi_set_error("bsi_dit_final_bwd: decoder P=%d unsupported (needs P = patch*patch*C <= %d)", P, BSI_DIT_MAX_P);
         return BSI_EINVAL;
     }
     const int Pp = (P + 7) / 8 * 8;
-    const bool wlds = (size_t)(P + 2) * d * sizeof(float) + 256 <= 128 * 1024;
-    const size_t lds = (size_t)(wlds ? P + 2 : 2) * d * sizeof(float) + 64 * sizeof(float);
+    const int npl = (P + 63) / 64;     // decoder columns per lane
+    const size_t nb = (size_t)64 * npl;  // bias-sum columns of the LDS region and of a slab
+    const bool wlds = (size_t)(P + 2) * d * sizeof(float) + nb * sizeof(float) <= 128 * 1024;
+    const size_t lds = (size_t)(wlds ? P + 2 : 2) * d * sizeof(float) + nb * sizeof(float);
     const int grid = final_bwd_grid(Mtok);
-#define LAUNCH_FB(V)                                                                                                   \
+#define LAUNCH_FB2(KERN)                                                                                               \
     do {                                                                                                               \
-        auto kern = wlds ? dit_final_bwd_kernel<V, true> : dit_final_bwd_kernel<V, false>;                             \
+        auto kern = KERN;                                                                                              \
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
         hipLaunchKernelGGL(kern, dim3(grid), dim3(TPB), lds, s, x, Mtok, d, P, Pp, ln_w, ln_b, dec_w, C, H, W, ps, g_xhat, \
                            c_out, coef_stride, dX, reinterpret_cast<__bf16*>(yb), reinterpret_cast<__bf16*>(dYb), parts);  \
+    } while (0)
+#define LAUNCH_FBW(V, NP) LAUNCH_FB2((wlds ? dit_final_bwd_wide_kernel<V, true, NP> : dit_final_bwd_wide_kernel<V, false, NP>))
+#define LAUNCH_FB(V)                                                                                      \
+    do {                                                                                                  \
+        if (npl == 1) LAUNCH_FB2((wlds ? dit_final_bwd_kernel<V, true> : dit_final_bwd_kernel<V, false>)); \
+        else if (npl == 2) LAUNCH_FBW(V, 2);                                                              \
+        else if (npl == 3) LAUNCH_FBW(V, 3);                                                              \
+        else LAUNCH_FBW(V, 4);                                                                            \
     } while (0)
     if (d <= 256) LAUNCH_FB(1);
     else if (d <= 1024) LAUNCH_FB(4);
     else LAUNCH_FB(8);
 #undef LAUNCH_FB
+#undef LAUNCH_FBW
+#undef LAUNCH_FB2
     BSI_CHECK_LAUNCH("bsi_dit_final_bwd");
-    // slabs [grid][2 d + 64] -> the three gradients, summed in slab order
-    const size_t stride = 2 * (size_t)d + 64;
+    // slabs [grid][2 d + 64 npl] -> the three gradients, summed in slab order
+    const size_t stride = 2 * (size_t)d + nb;
     int rc = bsi_reduce_slabs_launch(parts, stride, grid, (size_t)d, 0, d_ln_w, s);
     if (rc == BSI_OK) rc = bsi_reduce_slabs_launch(parts + d, stride, grid, (size_t)d, 0, d_ln_b, s);
     if (rc == BSI_OK && P % 4 == 0) {
         rc = bsi_reduce_slabs_launch(parts + 2 * (size_t)d, stride, grid, (size_t)P, 0, d_dec_b, s);
-    } else if (rc == BSI_OK) {  // odd decoder widths: sum the padded 64 columns behind the slabs, copy the first P
+    } else if (rc == BSI_OK) {  // odd decoder widths: sum the padded 64 npl columns behind the slabs, copy the first P
         float* tmp = parts + (size_t)grid * stride;
-        rc = bsi_reduce_slabs_launch(parts + 2 * (size_t)d, stride, grid, 64, 0, tmp, s);
+        rc = bsi_reduce_slabs_launch(parts + 2 * (size_t)d, stride, grid, nb, 0, tmp, s);
         if (rc == BSI_OK && hipMemcpyAsync(d_dec_b, tmp, (size_t)P * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess) {
             bsi_set_error("bsi_dit_final_bwd: bias gradient copy failed");
             rc = BSI_ELAUNCH;
@@ -873,7 +1046,10 @@ int bsi_dit_final_bwd_launch(const float* x, int Mtok, int d, int P, const float
     return rc;
 }
 
-size_t bsi_dit_final_bwd_parts_floats(int Mtok, int d) { return (size_t)final_bwd_grid(Mtok) * (2 * (size_t)d + 64) + 64; }
+size_t bsi_dit_final_bwd_parts_floats(int Mtok, int d, int P) {
+    const size_t nb = (size_t)64 * (P > 64 ? (P + 63) / 64 : 1);
+    return (size_t)final_bwd_grid(Mtok) * (2 * (size_t)d + nb) + nb;
+}
 
 extern "C" int bsi_silu_bwd_bf16(const float* ds, const float* pre, size_t n, void* out, bsi_stream_t stream) {
     BSI_CHECK_ARG(ds && out && n > 0, "bsi_silu_bwd_bf16: bad args");

@@ -36,7 +36,7 @@ inline int check_cfg(const bsi_dit_config* c) {
     BSI_CHECK_ARG(dh == 64 || dh == 128, "dit: head dim %d unsupported (64 or 128)", dh);
     const DitDims d = dims_of(c);
     BSI_CHECK_ARG(d.tokens % 64 == 0, "dit: %d tokens per image; must be a multiple of 64", d.tokens);
-    BSI_CHECK_ARG(d.P <= 64, "dit: patch*patch*C = %d > 64 unsupported", d.P);
+    BSI_CHECK_ARG(d.P <= BSI_DIT_MAX_P, "dit: decoder width P = patch*patch*C = %d unsupported (P <= %d)", d.P, BSI_DIT_MAX_P);
     BSI_CHECK_ARG((c->H * c->W) % 4 == 0, "dit: H*W must be a multiple of 4");
     return BSI_OK;
 }

@@ -2,6 +2,10 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+// widest patch decoder the engines run: P = patch * patch * C output columns per token (patch 8 on up to 4 channels).  The decoder
+// backward gives a lane ceil(P / 64) columns and has instances for 1 .. 4 (dit_bwd_ops.hip).
+constexpr int BSI_DIT_MAX_P = 256;
+
 int bsi_dit_prologue_launch(const float* mu, const float* c_in, int coef_stride, int B, int C, int H, int W, int ps,
                             int nmin, int nfreq, int kpad, void* out, hipStream_t s);
 int bsi_dit_final_launch(const float* x, int Mtok, int d, int P, const float* ln_w, const float* ln_b,

@@ -468,8 +468,9 @@ __global__ void dit_prologue_kernel(const float* __restrict__ mu, const float* _
 
 // dit.py:163-172,181 (+ bsi.py:382-386): per token LayerNorm(affine) -> Linear(dim -> P=ps*ps*C) in fp32 ->
 // unpatchify -> x_hat = fma(c_out, f, c_skip*mu).  dec_w (P x dim fp32) is staged in LDS once per workgroup;
-// each wave walks tokens with a grid stride.  WLDS = false (decoder larger than the LDS, e.g. DiT-L/4: 48 x 1024 fp32):
-// the weights are read through L1/L2 instead.
+// each wave walks tokens with a grid stride.  WLDS = false (decoder larger than 128 KB, e.g. DiT-L/4: 48 x 1024 fp32, DiT-L/8:
+// 192 x 1024 = 768 KB): the weights are read through L1/L2 instead.  P <= BSI_DIT_MAX_P = 256: nothing below depends on P but the
+// bounds of the output loop (16 outputs per round, the last round partial) and the LDS size, at most 128 KB (P 256 at d 128).
 template <int VPL, bool WLDS>
 __global__ void dit_final_kernel(const float* __restrict__ x, int Mtok, int d, int P, const float* __restrict__ ln_w,
                                  const float* __restrict__ ln_b, const float* __restrict__ dec_w,
@@ -789,8 +790,8 @@ int bsi_dit_final_launch(const float* x, int Mtok, int d, int P, const float* ln
                          const float* c_skip, const float* c_out, int coef_stride, const void* delta, const float* gate,
                          int gate_rows, int gate_stride, float* out, hipStream_t s) {
     size_t lds = (size_t)P * d * sizeof(float);
-    if (P > 64) {
-        bsi_set_error("bsi_dit_final: decoder P=%d unsupported (needs patch*patch*C <= 64)", P);
+    if (P < 1 || P > BSI_DIT_MAX_P) {
+        bsi_set_error("bsi_dit_final: decoder P=%d unsupported (needs P = patch*patch*C <= %d)", P, BSI_DIT_MAX_P);
         return BSI_EINVAL;
     }
     const bool wlds = lds <= 128 * 1024;  // (reading the weights from L2 instead measures the same: 26 vs 27 ms per 129 launches)

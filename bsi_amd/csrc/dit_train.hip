@@ -15,7 +15,7 @@ int bsi_dit_final_bwd_launch(const float* x, int Mtok, int d, int P, const float
                              const float* dec_w, int C, int H, int W, int ps, const float* g_xhat, const float* c_out,
                              int coef_stride, float* dX, void* yb, void* dYb, float* d_dec_b, float* d_ln_w,
                              float* d_ln_b, float* parts, hipStream_t s);
-size_t bsi_dit_final_bwd_parts_floats(int Mtok, int d);
+size_t bsi_dit_final_bwd_parts_floats(int Mtok, int d, int P);
 
 namespace {
 
@@ -74,6 +74,9 @@ inline bool train_geometry_ok(const Dims& d) {
     return d.tokens > 0 && d.tokens % 64 == 0 && d.tokens <= 1024 && d.dim % 64 == 0 && (dh == 64 || dh == 128) && d.dim <= 1024;
 }
 
+// decoder columns of a token as the weight-gradient GEMM sees them: P rounded up to 8, zero padded
+inline int dec_pp(const Dims& d) { return (d.P + 7) / 8 * 8; }
+
 inline Tape carve_tape(const Dims& d, int B, void* base) {
     Tape t;
     char* p = reinterpret_cast<char*>(base);
@@ -125,6 +128,7 @@ struct BwdWs {
     char* dd;      // bf16 [M, dim]     gradient of a branch delta
     char* dbig;    // bf16 [M, 4 dim]   dhp / dqkv
     char* dsmall;  // bf16 [M, dim]     dxn / dao
+    char* dyb;     // bf16 [M, Pp]      decoder output gradient, operand of the decoder's weight-gradient GEMM (Pp may exceed dim)
     float* dmod;   // fp32 [2 (block parity)][tokens / 64 planes][B, 6 dim]: per-slab sums of the modulation gradients (reproducible: no atomics)
     char* dmod_bf; // bf16 [B, 6 dim]
     float* fin_parts;  // per-block sums of the final layer's parameter gradients (bsi_dit_final_bwd_launch)
@@ -132,7 +136,7 @@ struct BwdWs {
     char* dpre_bf; // bf16 [B, dim]
     char* tn;      // TN GEMM slabs
     char* cs;      // colsum slabs
-    float* decw;   // fp32 [64, dim]   decoder weight gradient with its rows padded to a multiple of 8
+    float* decw;   // fp32 [Pp, dim]   decoder weight gradient with its rows padded to a multiple of 8
     // bias gradients taken where dY is produced (round 4): per-slab column sums, reduced once per block by bsi_colsum_rows_f32
     float* rows_fc2;  // fp32 [M / 64][dim]      sums of the dd2 rows (written by the kernel that writes ws.dd for the MLP branch)
     float* rows_out;  // fp32 [M / 64][dim]      sums of the dd1 rows
@@ -151,14 +155,22 @@ inline BwdWs carve_bwd(const Dims& d, int B, void* base) {
     w.dd = p + off; off += au(M * dim * 2);
     w.dbig = p + off; off += au(M * 4 * dim * 2);
     w.dsmall = p + off; off += au(M * dim * 2);
+    w.dyb = p + off; off += au(M * (size_t)dec_pp(d) * 2);
     w.dmod = reinterpret_cast<float*>(p + off); off += au((size_t)2 * (d.tokens / 64 > 0 ? d.tokens / 64 : 1) * B * 6 * dim * 4);
     w.dmod_bf = p + off; off += au((size_t)B * 6 * dim * 2);
-    w.fin_parts = reinterpret_cast<float*>(p + off); off += au(bsi_dit_final_bwd_parts_floats((int)d.M, (int)dim) * 4);
+    w.fin_parts = reinterpret_cast<float*>(p + off); off += au(bsi_dit_final_bwd_parts_floats((int)d.M, (int)dim, d.P) * 4);
     w.ds = reinterpret_cast<float*>(p + off); off += au((size_t)B * dim * 4);
     w.dpre_bf = p + off; off += au((size_t)B * dim * 2);
-    w.tn = p + off; off += au(bsi_gemm_tn_workspace_bytes((int)M, 4 * (int)dim, (int)dim));
+    {   // slabs of the widest weight gradient: fc1 / fc2 [4 dim, dim], the patch encoder [dim, kpad] (kpad > 4 dim at patch 8 with
+        // Fourier features on a narrow model), the decoder [Pp, dim]
+        size_t tn = bsi_gemm_tn_workspace_bytes((int)M, 4 * (int)dim, (int)dim);
+        const size_t enc = bsi_gemm_tn_workspace_bytes((int)M, (int)dim, d.kpad), dec = bsi_gemm_tn_workspace_bytes((int)M, dec_pp(d), (int)dim);
+        tn = tn > enc ? tn : enc;
+        tn = tn > dec ? tn : dec;
+        w.tn = p + off; off += au(tn);
+    }
     w.cs = p + off; off += au(bsi_colsum_workspace_bytes(6 * (int)dim));
-    w.decw = reinterpret_cast<float*>(p + off); off += au((size_t)64 * dim * 4);
+    w.decw = reinterpret_cast<float*>(p + off); off += au((size_t)(dec_pp(d) > 64 ? dec_pp(d) : 64) * dim * 4);
     const size_t r64 = (M + 63) / 64, r128 = (M + 127) / 128;
     w.rows_fc2 = reinterpret_cast<float*>(p + off); off += au(r64 * dim * 4);
     w.rows_out = reinterpret_cast<float*>(p + off); off += au(r64 * dim * 4);
@@ -255,6 +267,7 @@ extern "C" int bsi_dit_train_forward(const bsi_dit_config* cfg, const bsi_dit_we
     const Dims d = dims_of(cfg, B);
     BSI_CHECK_ARG(train_geometry_ok(d), "bsi_dit_train_forward: unsupported geometry (tokens %d, dim %d, head dim %d)", d.tokens, d.dim,
                   d.heads > 0 ? d.dim / d.heads : 0);
+    BSI_CHECK_ARG(d.P >= 1 && d.P <= BSI_DIT_MAX_P, "bsi_dit_train_forward: decoder width P = patch*patch*C = %d unsupported (P <= %d)", d.P, BSI_DIT_MAX_P);
     const int dim = d.dim, M = (int)d.M, dh = d.dim / d.heads;
     const int mod_stride = d.depth * 6 * dim;
     Tape tp = carve_tape(d, B, tape_mem);
@@ -371,6 +384,7 @@ extern "C" int bsi_dit_backward(const bsi_dit_config* cfg, const bsi_dit_weights
     const Dims d = dims_of(cfg, B);
     BSI_CHECK_ARG(train_geometry_ok(d), "bsi_dit_backward: unsupported geometry (tokens %d, dim %d, head dim %d)", d.tokens, d.dim,
                   d.heads > 0 ? d.dim / d.heads : 0);
+    BSI_CHECK_ARG(d.P >= 1 && d.P <= BSI_DIT_MAX_P, "bsi_dit_backward: decoder width P = patch*patch*C = %d unsupported (P <= %d)", d.P, BSI_DIT_MAX_P);
     const int dim = d.dim, M = (int)d.M, dh = d.dim / d.heads;
     const int mod_stride = d.depth * 6 * dim;
     Tape tp = carve_tape(d, B, tape_mem);
@@ -396,12 +410,11 @@ extern "C" int bsi_dit_backward(const bsi_dit_config* cfg, const bsi_dit_weights
     };
     // decoder: dX = d/dx_final, parameter gradients of patch_decoder (dit.py:163-165)
     {
-        const int Pp = (d.P + 7) / 8 * 8;  // yb -> ws.dd, dYb -> ws.dsmall (Pp <= 64 <= dim columns)
-        BSI_CHECK_ARG(Pp <= dim, "bsi_dit_backward: decoder width %d exceeds dim %d", Pp, dim);
+        const int Pp = dec_pp(d);  // yb -> ws.dd, dYb -> ws.dyb
         TRY(bsi_dit_final_bwd_launch(tp.x, M, dim, d.P, w->dec_ln_w, w->dec_ln_b, w->dec_w, cfg->C, cfg->H, cfg->W,
-                                     cfg->patch, g_out, c_out, 1, ws.dX, ws.dd, ws.dsmall, g->dec_b, g->dec_ln_w,
+                                     cfg->patch, g_out, c_out, 1, ws.dX, ws.dd, ws.dyb, g->dec_b, g->dec_ln_w,
                                      g->dec_ln_b, ws.fin_parts, s));
-        TRY(bsi_gemm_tn_bf16(ws.dsmall, Pp, ws.dd, dim, M, Pp, dim, ws.decw, dim, 0, ws.tn, stream));
+        TRY(bsi_gemm_tn_bf16(ws.dyb, Pp, ws.dd, dim, M, Pp, dim, ws.decw, dim, 0, ws.tn, stream));
         if (hipMemcpyAsync(g->dec_w, ws.decw, (size_t)d.P * dim * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess) {
             bsi_set_error("bsi_dit_backward: decoder gradient copy failed");
             return BSI_ELAUNCH;

@@ -110,7 +110,9 @@ class DenoisingDiT(nn.Module):
     Any `heads` builds, as in the reference; the kernels decide at first use.  Sampling and ELBO run head dims (dim / heads) 64 and
     128 at any multiple of 64 tokens; training runs the same head dims at up to 1024 tokens, dim <= 1024, with or without dropout
     (e.g. the paper's CIFAR-10 model: dim 128, one head, patch 2).  Other geometries raise a RuntimeError naming tokens, dim and
-    head dim."""
+    head dim.  Any `patch_size` builds too; sampling, ELBO and training run decoder widths P = patch_size**2 * channels up to 256
+    -- patch 2, 4 and 8 on RGB images (patch 8: P = 192, and 1344 encoder columns with Fourier features 6..8), P wider than dim
+    included -- and a wider decoder raises a RuntimeError naming P."""
 
     def __init__(self, data_shape, patch_size: int, dim: int, depth: int, heads: int, dropout: float | None = None,
                  fourier_features: FourierFeatures | None = None, **kwargs):

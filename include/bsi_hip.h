@@ -343,7 +343,8 @@ int bsi_cast_transpose_bf16(const float* in, int rows, int cols, void* out, int 
  * ---------------------------------------------------------------------------------------- */
 typedef struct bsi_dit_config {
     int C, H, W;     /* data_shape */
-    int patch;       /* patch_size */
+    int patch;       /* patch_size; the decoder width P = patch*patch*C must be <= 256 (patch 8 on up to 4 channels): every
+                      * engine entry refuses a wider one, naming P, before it follows a pointer */
     int dim, depth, heads;
     int ff_nmin, ff_nmax; /* FourierFeatures n_min..n_max (fourier_features.py:11-19); ff_nmin > ff_nmax = none */
 } bsi_dit_config;
@@ -361,7 +362,7 @@ typedef struct bsi_dit_weights {
     const float* t_bias;   /* [dim]                                                           */
     const float* dec_ln_w; /* [dim] patch_decoder.0 */
     const float* dec_ln_b;
-    const float* dec_w;    /* fp32 [patch*patch*C][dim] patch_decoder.1 */
+    const float* dec_w;    /* fp32 [P = patch*patch*C][dim] patch_decoder.1, P <= 256; stays fp32 (the accuracy contract of x_hat) */
     const float* dec_b;
     const bsi_dit_block_weights* blocks; /* host array [depth] */
 } bsi_dit_weights;
@@ -668,7 +669,9 @@ size_t bsi_dit_tape_bytes(const bsi_dit_config* cfg, int B);
 size_t bsi_dit_backward_workspace_bytes(const bsi_dit_config* cfg, int B);
 /* out = c_skip*mu + c_out*f(c_in*mu, t) (or f(mu, t) with NULL coefficients), per-sample t/coefficients [B];
  * records the activations the backward needs in `tape` (bsi_dit_tape_bytes).  Geometries: dim / heads 64 or 128, tokens % 64 == 0
- * up to 1024, dim <= 1024; bsi_dit_backward refuses the same others. */
+ * up to 1024, dim <= 1024, decoder width P = patch*patch*C <= 256 (P may exceed dim); bsi_dit_backward refuses the same others.
+ * bsi_dit_backward_workspace_bytes grows with P (decoder weight gradient [P rounded up to 8, dim], its bf16 operand, the
+ * per-workgroup bias sums) and with kpad (the patch encoder's weight-gradient slabs when kpad > 4 dim). */
 int bsi_dit_train_forward(const bsi_dit_config* cfg, const bsi_dit_weights* w /*host*/, int B, const float* mu,
                           const float* t, const float* c_in, const float* c_skip, const float* c_out, float* out,
                           void* tape, float dropout_p, unsigned long long seed, bsi_stream_t stream);
