@@ -167,6 +167,10 @@ inline BwdWs carve_bwd(const Dims& d, int B, void* base) {
         const size_t enc = bsi_gemm_tn_workspace_bytes((int)M, (int)dim, d.kpad), dec = bsi_gemm_tn_workspace_bytes((int)M, dec_pp(d), (int)dim);
         tn = tn > enc ? tn : enc;
         tn = tn > dec ? tn : dec;
+        // the adaLN output layer [6 dim, dim] over B sample rows: one token range, written in place, below 1024 images; from there on
+        // tn_splits may cut the samples in two, and the bias-gradient slabs of bsi_gemm_tn_bias_bf16 lie behind 16 x 6 dim x dim floats
+        const size_t ada = bsi_gemm_tn_workspace_bytes(B, 6 * (int)dim, (int)dim);
+        tn = tn > ada ? tn : ada;
         w.tn = p + off; off += au(tn);
     }
     w.cs = p + off; off += au(bsi_colsum_workspace_bytes(6 * (int)dim));
