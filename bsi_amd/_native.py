@@ -365,3 +365,8 @@ def ptr(t):
 
 def stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def upload_table(arr, device):
+    """The bytes of a ctypes array of descriptors as a uint8 tensor on `device` (a synchronous host-to-device copy)."""
+    return torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(device)

@@ -9,6 +9,7 @@ from torch import Tensor, nn
 
 from . import _native as N
 from .bsi import Discretization, _new, _PredictCombine, _SqErr
+from .models.native import native_denoiser
 
 
 class _Clip(torch.autograd.Function):
@@ -87,8 +88,7 @@ class BFN(nn.Module):
         return alpha, rho, wdisc
 
     def _native_model(self):
-        m = self.model
-        return m if hasattr(m, "forward_native") and hasattr(m, "adaln_table") else None
+        return native_denoiser(self.model)
 
     # -- ELBO (bfn.py:59-123) ----------------------------------------------------------------------------
     def _assemble(self, l_recon, l_latent, n_recon_samples, n_measure_samples, estimate_var):

@@ -15,6 +15,7 @@ import torch
 from torch import Tensor, nn
 
 from . import _native as N
+from .models.native import native_denoiser
 
 
 @dataclass
@@ -215,8 +216,7 @@ class BSI(nn.Module):
             raise RuntimeError("bsi_amd.BSI: module is not on a HIP device; there is no CPU path")
 
     def _native_model(self):
-        m = self.model
-        return m if hasattr(m, "forward_native") and hasattr(m, "adaln_table") else None
+        return native_denoiser(self.model)
 
     def _schedule(self, t: Tensor):
         """lam = icdf(t), alpha = diff(lam), EDM coefficients over the schedule (bsi.py:322-323,396-403)."""

@@ -17,6 +17,7 @@ import torch
 import torch.distributed as dist
 
 from . import _native as N
+from .models.native import native_denoiser
 
 
 def split_batch(batch_size: int, world_size: int, rank: int) -> int:
@@ -334,15 +335,11 @@ class DPTrainer:
         self.stage_events = []
         self.step_count = 0
         self.ema_beta, self.ema_after = ema_beta, ema_update_after_step
-        self._invalidate(self.model)
-        self.model._ws = None
+        self._invalidate(self.model, plans=True)  # persistent buffers + ctypes tables are rebuilt on demand
         # (`_flat_grad_only` -- the HIP backward leaves its flat gradient in `_last_flat_grad` and hands autograd no per-parameter
         # gradients -- is set only INSIDE `_backward`: a sticky attribute would silently turn every ordinary `loss.backward()` on
         # this model, and on the deep-copied EMA model, into a no-op for `p.grad`)
         self.model._flat_grad_only = False
-        for attr in ("_plan", "_plan_t", "_grad_buffer"):  # persistent buffers + ctypes tables (rebuilt on demand; not deep-copyable)
-            if hasattr(self.model, attr):
-                setattr(self.model, attr, None)
         self._ema_model = copy.deepcopy(self.model).eval().requires_grad_(False) if ema else None
         pad = self.lay_world * SEG_ALIGN
         self.fp = FlatParams(self.model, pad)
@@ -373,7 +370,7 @@ class DPTrainer:
     #    testable with world-size-2 gloo processes that substitute the device stages (tests/test_dp_host.py)
     def _seg_table(self, rows, dev):
         arr = (N.Seg * len(rows))(*[N.Seg(*r) for r in rows])
-        return torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(dev)
+        return N.upload_table(arr, dev)
 
     def _setup_update_state(self, dev):
         n = self.fp.flat.numel()
@@ -487,7 +484,7 @@ class DPTrainer:
             if self.comm_stream is not None:
                 torch.cuda.current_stream().wait_stream(self.comm_stream)
             self._gates_pending = False
-        self.model.__dict__["_params_pending_sync"] = None
+        self.model._params_pending_sync = None
 
     def _install_gates(self):
         """Before the forward of a step whose parameters are still arriving: hand the per-bucket events and the per-part cast
@@ -511,7 +508,7 @@ class DPTrainer:
         self._gate_arr = arr  # stays alive until cleared
         N.check(N.lib().bsi_dit_train_forward_set_gates(arr, n))
         self._gates_pending = False
-        self.model.__dict__["_params_pending_sync"] = None
+        self.model._params_pending_sync = None
         return True
 
     def _exchange(self, flat_g):
@@ -610,9 +607,10 @@ class DPTrainer:
         return a, b
 
     # ------------------------------------------------------------------------------------------------
-    def _invalidate(self, model):
-        model._pack = None
-        model._pack_t = None
+    def _invalidate(self, model, plans=False):
+        """The parameters were written by a raw kernel or a collective: a native denoiser (models/native.py) forgets its cast shadows."""
+        if native_denoiser(model) is not None:
+            model.invalidate_native(plans)
 
     def train_step(self, x: torch.Tensor, generator=None) -> torch.Tensor:
         """One optimizer step on this rank's shard `x`; returns the (local) mean loss (detached)."""

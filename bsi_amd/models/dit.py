@@ -13,6 +13,7 @@ from torch import Tensor, nn
 
 from .. import _native as N
 from ..nn import FourierFeatures
+from .native import NativeDenoiser, native_forward_train
 from .pos_emb import NyquistPositionalEmbedding
 
 
@@ -104,7 +105,7 @@ class DiT(nn.Module):
         self.patch_decoder = nn.Sequential(nn.LayerNorm(hidden_size), nn.Linear(hidden_size, patch_area * out_channels))
 
 
-class DenoisingDiT(nn.Module):
+class DenoisingDiT(NativeDenoiser):
     """Diffusion Transformer denoiser f(mu, t) — same constructor as bsi.models.dit.DenoisingDiT.
 
     Any `heads` builds, as in the reference; the kernels decide at first use.  Sampling and ELBO run head dims (dim / heads) 64 and
@@ -128,12 +129,6 @@ class DenoisingDiT(nn.Module):
                        out_channels=out_channels, hidden_size=dim, depth=depth, heads=heads, mlp_ratio=4,
                        dropout=dropout)
         self._cfg_args = dict(patch=patch_size, dim=dim, depth=depth, heads=heads)
-        self._pack = None       # cached bf16 weight shadows + ctypes tables
-        self._pack_key = None
-        self._ws = None         # cached workspace tensor
-        self._pack_t = None     # cached transposed shadows (training)
-        self._pack_t_key = None
-        self._plan = None       # persistent shadow buffers + descriptor table of the one-launch cast
         self.cu_pair = "env"    # (h_cus, flags) | None | "env" (= BSI_CU_PAIR): two CU-masked streams for large inference batches
 
     # ------------------------------------------------------------------------------------------------
@@ -145,35 +140,6 @@ class DenoisingDiT(nn.Module):
         a = self._cfg_args
         return N.DitConfig(Cc, H, W, a["patch"], a["dim"], a["depth"], a["heads"],
                            ff.n_min if ff is not None else 1, ff.n_max if ff is not None else 0)
-
-    _NATIVE_CACHES = ("_pack", "_pack_key", "_pack_t", "_pack_t_key", "_plan", "_plan_t", "_ws", "_last_flat_grad", "_grad_buffer",
-                      "_params_pending_sync", "_bwd_sched")
-
-    def __deepcopy__(self, memo):
-        """`copy.deepcopy(model)` (EMA copies, checkpoint tooling) after the model has run: the native caches hold ctypes tables with raw
-        device pointers into THIS model's buffers -- they are neither picklable nor valid for a copy, and are rebuilt on first use."""
-        import copy
-        saved = {k: self.__dict__.pop(k) for k in self._NATIVE_CACHES if k in self.__dict__}
-        try:
-            cls = self.__class__
-            new = cls.__new__(cls)
-            memo[id(self)] = new
-            new.__dict__ = copy.deepcopy(self.__dict__, memo)
-            for k in saved:
-                new.__dict__[k] = None
-        finally:
-            self.__dict__.update(saved)
-        return new
-
-    def _weights_key(self):
-        ps = list(self.parameters())
-        return (ps[0].device, ps[0].data_ptr(), sum(p._version for p in ps))
-
-    def _storage_key(self):
-        """Identity of the parameters' STORAGE: the pack plan bakes every parameter's raw pointer into a device-side descriptor table
-        and into the ctypes weight tables, so replacing the storage of a parameter must rebuild the plan."""
-        ps = list(self.parameters())
-        return (ps[0].device, len(ps), hash(tuple(p.data_ptr() for p in ps)))
 
     def _build_plan(self, skey):
         """Persistent bf16 shadows ([N][K] row-major) of the GEMM weights, the ctypes weight table pointing at them and at the fp32
@@ -241,8 +207,7 @@ class DenoisingDiT(nn.Module):
             arr[i] = N.CastDesc(src.data_ptr(), dst.data_ptr() if dst is not None else None,
                                 dst_t.data_ptr() if dst_t is not None else None, rows, cols, ld, ld_t, tiles, 0)
             tiles += lib.bsi_cast_batch_tiles(rows, cols, ld if dst is not None else cols)
-        raw = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8)
-        plan["table"] = (raw.to(plan["descs"][0][0].device), len(plan["descs"]), tiles)
+        plan["table"] = (N.upload_table(arr, plan["descs"][0][0].device), len(plan["descs"]), tiles)
         # The same descriptors grouped by the GATES of a gated training forward (bsi_dit_train_forward_set_gates): [0] the patch
         # encoder (the last descriptor), [1 + l] the six matrices of block l, [depth + 1] nothing -- one device table of sub-tables
         # whose tile0 restart at 0, and per gate (first descriptor, count, tiles).
@@ -261,8 +226,7 @@ class DenoisingDiT(nn.Module):
                     t0 += lib.bsi_cast_batch_tiles(rows, cols, ld if dst is not None else cols)
                 spans.append((pos, len(idx), t0))
                 pos += len(idx)
-            raw_g = torch.frombuffer(bytearray(bytes(sub)), dtype=torch.uint8).to(plan["descs"][0][0].device)
-            plan["gate_tables"] = (raw_g, spans)
+            plan["gate_tables"] = (N.upload_table(sub, plan["descs"][0][0].device), spans)
         else:
             plan["gate_tables"] = None
 
@@ -271,10 +235,7 @@ class DenoisingDiT(nn.Module):
         gated training forward of a sharded data-parallel step, DPTrainer).  Marks the shadows as current for this parameter
         version -- the caller's casts are enqueued in front of every use."""
         key = self._weights_key()
-        skey = self._storage_key()
-        if getattr(self, "_plan", None) is None or self._plan["skey"] != skey:
-            self._plan = self._build_plan(skey)
-        plan = self._plan
+        plan = self._current_plan()
         self._pack, self._pack_key = plan["pack"], key
         if plan["pack_t"] is not None:
             self._pack_t, self._pack_t_key = plan["pack_t"], key
@@ -288,13 +249,9 @@ class DenoisingDiT(nn.Module):
         key = self._weights_key()
         if self._pack is not None and self._pack_key == key:
             return self._pack
-        sync = self.__dict__.get("_params_pending_sync")
-        if sync is not None:  # a trainer's all-gather of these parameters is still in flight on another stream: wait for it first
-            sync()
-        skey = self._storage_key()
-        if getattr(self, "_plan", None) is None or self._plan["skey"] != skey:
-            self._plan = self._build_plan(skey)
-        plan = self._plan
+        if self._params_pending_sync is not None:  # a trainer's all-gather of these parameters is still in flight on another stream
+            self._params_pending_sync()
+        plan = self._current_plan()
         table, n, tiles = plan["table"]
         with torch.no_grad():
             N.check(N.lib().bsi_cast_batch_bf16(N.ptr(table), n, tiles, N.stream()))
@@ -302,11 +259,6 @@ class DenoisingDiT(nn.Module):
         if plan["pack_t"] is not None:  # the table carries the transposed shadows too
             self._pack_t, self._pack_t_key = plan["pack_t"], key
         return self._pack
-
-    def _workspace(self, nbytes: int, dev):
-        if self._ws is None or self._ws.numel() < nbytes or self._ws.device != dev:
-            self._ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        return self._ws
 
     def adaln_table(self, t: Tensor) -> Tensor:
         """adaLN modulation rows for the times `t` ([R] fp32): returns fp32 [R, depth, 6*dim]
@@ -327,13 +279,7 @@ class DenoisingDiT(nn.Module):
         `mod`: [1 or B, depth, 6*dim] rows of `adaln_table`."""
         cfg, w, _, _ = self.native_pack()
         lib = N.lib()
-        if mu.dtype != torch.float32:
-            raise RuntimeError("bsi_amd.DenoisingDiT: input must be fp32 (bf16 is used inside the kernels)")
-        mu = mu.contiguous()
-        B = mu.shape[0]
-        assert tuple(mu.shape[1:]) == self.data_shape, f"expected [B,{self.data_shape}], got {tuple(mu.shape)}"
-        if out is None:
-            out = torch.empty_like(mu)
+        mu, B, out = self._prepare_input(mu, out)
         ws = self._workspace(lib.bsi_dit_workspace_bytes(C.byref(cfg), B), mu.device)
         tokens = None
         if return_tokens:
@@ -351,16 +297,18 @@ class DenoisingDiT(nn.Module):
         return (out, tokens) if return_tokens else out
 
     def forward_train(self, mu: Tensor, t: Tensor, c_in=None, c_skip=None, c_out=None) -> Tensor:
-        """Differentiable evaluation (parameters only): tape-recording HIP forward + hand-written HIP backward."""
-        from .dit_train import dit_forward_train
-        return dit_forward_train(self, mu, t, c_in, c_skip, c_out)
+        """Differentiable evaluation (parameters only): tape-recording HIP forward + hand-written HIP backward.  In `train()` mode
+        the blocks' dropout (attention weights and MLP input, dit.py:43-44,70,101) is applied with a counter-based mask."""
+        p = float(self.dit.blocks[0].attn.dropout) if self.training else 0.0
+        return native_forward_train(self, p, mu, t, c_in, c_skip, c_out)
 
-    def forward(self, mu: Tensor, t: Tensor) -> Tensor:
-        """f(mu, t): mu [B, *data_shape] fp32, t [B] in [0, 1]  (dit.py:225-233)."""
-        if not mu.is_cuda:
-            raise RuntimeError("bsi_amd.DenoisingDiT: input is not on a HIP device; there is no CPU path")
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
-            from .dit_train import dit_forward_autograd  # backward kernels live in the training engine
-            return dit_forward_autograd(self, mu, t)
-        mod = self.adaln_table(t)
-        return self.forward_native(mu, mod)
+    def _tape_bytes(self, cfg, B):
+        return N.lib().bsi_dit_tape_bytes(C.byref(cfg), B)
+
+    def _engine_train_forward(self, cfg, w, B, mu, t, c_in, c_skip, c_out, out, tape, drop_p, seed):
+        N.check(N.lib().bsi_dit_train_forward(C.byref(cfg), C.byref(w), B, N.ptr(mu), N.ptr(t), N.ptr(c_in), N.ptr(c_skip),
+                                              N.ptr(c_out), N.ptr(out), N.ptr(tape), drop_p, seed, N.stream()))
+
+    def _engine_backward(self, ctx, g_out, flat):
+        from .dit_train import engine_backward  # the gradient tables live with the training engine
+        return engine_backward(self, ctx, g_out, flat)

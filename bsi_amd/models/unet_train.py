@@ -1,5 +1,5 @@
-"""Training path of the native DenoisingVDMUNet: a `torch.autograd.Function` whose forward records a tape in device
-memory (`bsi_unet_train_forward`) and whose backward is the hand-written HIP backward (`bsi_unet_backward`).
+"""Training path of the native DenoisingVDMUNet behind the shared `torch.autograd.Function` (models/native.py): its forward records
+a tape in device memory (`bsi_unet_train_forward`), its backward is the hand-written HIP backward (`bsi_unet_backward`) below.
 torch's autograd only carries the parameter gradients out; no torch op computes anything.
 
 Replaces autograd over bsi/models/vdm_unet.py:92-100, bsi/nn/simplified_unet.py:33-48, bsi/nn/residual_block.py:61-64 and
@@ -10,6 +10,7 @@ import torch
 from torch import Tensor, nn
 
 from .. import _native as N
+from .native import flat_grad_views
 
 
 def _block_names(model):
@@ -23,16 +24,9 @@ def _grad_plan(model, cfg, flat, key):
     addresses, the staging buffers of the stacked FiLM gradient and the padded pos_map.1 gradient, and the device table of the
     copies that scatter them (and the shared conv2 / skip bias gradients) to their parameters' places."""
     lib = N.lib()
-    dev = flat.device
     dim, cd = cfg.dim, cfg.c_dim
-    named = dict(model.named_parameters())
-    order = list(named)
-    total = sum(q.numel() for q in named.values())
-    assert flat.numel() >= total and flat.dtype == torch.float32 and flat.is_contiguous()
-    views, off = {}, 0
-    for n in order:
-        views[n] = flat[off:off + named[n].numel()].view_as(named[n])
-        off += named[n].numel()
+    flat, views, order = flat_grad_views(model, flat)
+    dev = flat.device
     names = _block_names(model)
     blocks_m = model._blocks()
     arr = (N.UNetResBlockGrads * len(names))()
@@ -81,7 +75,7 @@ def _grad_plan(model, cfg, flat, key):
             assert d.is_contiguous() and s_.is_contiguous() and d.numel() == s_.numel()
             descs[i].src, descs[i].dst, descs[i].len, descs[i].tile0 = s_.data_ptr(), d.data_ptr(), d.numel(), tiles
             tiles += lib.bsi_copy_batch_tiles(d.numel())
-        plan.update(copy_table=torch.frombuffer(bytearray(bytes(descs)), dtype=torch.uint8).to(dev), copy_n=len(dst), copy_tiles=tiles)
+        plan.update(copy_table=N.upload_table(descs, dev), copy_n=len(dst), copy_tiles=tiles)
     return plan
 
 
@@ -89,13 +83,10 @@ def transposed_pack(model):
     """bf16 shadows for the input-gradient products (rotated conv weights, transposed Linear weights), cached per parameter
     version like `native_pack`: persistent buffers, one batched launch for all convolution weights."""
     key = model._weights_key()
-    if getattr(model, "_pack_t", None) is not None and model._pack_t_key == key:
+    if model._pack_t is not None and model._pack_t_key == key:
         return model._pack_t
     lib = N.lib()
-    skey = model._storage_key()
-    if getattr(model, "_plan_t", None) is None or model._plan_t["skey"] != skey:
-        model._plan_t = _build_plan_t(model, skey)
-    plan = model._plan_t
+    plan = model._current_plan("_plan_t")
     with torch.no_grad():
         N.check(lib.bsi_conv_weight_pack_batch(N.ptr(plan["descs"]), plan["ndesc"], 1, N.stream()))
         torch.cat(plan["film_ws"], dim=0, out=plan["film_w_cat"])
@@ -106,7 +97,7 @@ def transposed_pack(model):
     return model._pack_t
 
 
-def _build_plan_t(model, skey):
+def build_plan_t(model, skey):
     dev = model.encode.weight.device
     keep, descs, lin = [], [], []
 
@@ -146,75 +137,38 @@ def _build_plan_t(model, skey):
     wt.film_wT = lin_t(film_w_cat)
     wt.pm3_wT = lin_t(model.pos_map[3].weight.detach())
     darr = (N.ConvPackDesc * len(descs))(*descs)
-    descs_dev = torch.frombuffer(bytearray(bytes(darr)), dtype=torch.uint8).to(dev)
+    descs_dev = N.upload_table(darr, dev)
     keep.extend([film_ws, film_w_cat, descs_dev])
     return {"skey": skey, "pack": (wt, arr, keep), "descs": descs_dev, "ndesc": len(descs), "lin_t": lin, "film_ws": film_ws,
             "film_w_cat": film_w_cat}
 
 
-class _UNetTrainFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, model, drop_p, seed, mu, t, c_in, c_skip, c_out, *params):
-        lib = N.lib()
-        cfg, w, _, _ = model.native_pack()
-        mu = mu.contiguous()
-        t = t.detach().to(torch.float32).contiguous()
-        B = mu.shape[0]
-        out = torch.empty_like(mu)
-        tape = torch.empty(lib.bsi_unet_tape_bytes(C.byref(cfg), B), dtype=torch.uint8, device=mu.device)
-        N.check(lib.bsi_unet_train_forward(C.byref(cfg), C.byref(w), B, N.ptr(mu), N.ptr(t), N.ptr(c_in), N.ptr(c_skip),
-                                           N.ptr(c_out), N.ptr(out), N.ptr(tape), drop_p, seed, N.stream()))
-        ctx.model, ctx.tape, ctx.c_out, ctx.B = model, tape, c_out, B
-        ctx.drop = (drop_p, seed)
-        return out
-
-    @staticmethod
-    def backward(ctx, g_out):
-        lib = N.lib()
-        model, B = ctx.model, ctx.B
-        cfg, w, _, _ = model.native_pack()
-        wt, _, _ = transposed_pack(model)
-        dev = g_out.device
-        g_out = g_out.contiguous()
-        flat = getattr(model, "_grad_buffer", None)  # the data-parallel trainer's persistent (padded) gradient buffer, if any
-        if flat is not None:
-            # persistent buffer: the views, the gradient tables and the copy jobs are built once per (buffer, parameter storage) --
-            # ~760 tensor views and ~170 descriptors per step otherwise, a few ms of host time in front of the backward's first launch
-            key = (flat.data_ptr(), flat.numel(), model._storage_key())
-            plan = getattr(model, "_plan_g", None)
-            if plan is None or plan["key"] != key:
-                plan = model._plan_g = _grad_plan(model, cfg, flat, key)
-        else:
-            total = sum(q.numel() for q in model.parameters())
-            plan = _grad_plan(model, cfg, torch.empty(total, dtype=torch.float32, device=dev), None)
-        flat, views, g = plan["flat"], plan["views"], plan["g"]
-        ws = torch.empty(lib.bsi_unet_backward_workspace_bytes(C.byref(cfg), B), dtype=torch.uint8, device=dev)
-        N.check(lib.bsi_unet_backward(C.byref(cfg), C.byref(w), C.byref(wt), C.byref(g), B, N.ptr(g_out), N.ptr(ctx.c_out),
-                                      N.ptr(ctx.tape), N.ptr(ws), ctx.drop[0], ctx.drop[1], N.stream()))
-        ctx.tape = None
-        # the stacked FiLM gradients and the shared skip / conv2 bias gradients go to their parameters' places in the flat buffer:
-        # one launch of bsi_copy_batch_f32 instead of 167 when the buffer is the trainer's (torch._foreach_copy_ issues a hipMemcpyAsync per pair on ROCm)
-        if plan["copy_table"] is not None:
-            N.check(lib.bsi_copy_batch_f32(N.ptr(plan["copy_table"]), plan["copy_n"], plan["copy_tiles"], N.stream()))
-        else:  # a fresh gradient buffer per call (plain autograd): no table to upload, no synchronisation
-            torch._foreach_copy_(plan["copy_dst"], plan["copy_src"])
-        views["pos_map.1.weight"].copy_(plan["pm1_pad"][:, :views["pos_map.1.weight"].shape[1]])
-        model._last_flat_grad = flat
-        if getattr(model, "_flat_grad_only", False):
-            # the data-parallel trainer consumes `_last_flat_grad` itself: handing the views to autograd would make it copy every
-            # one of them into a .grad tensor nobody reads (one copy kernel per parameter tensor)
-            return (None,) * (8 + len(plan["order"]))
-        return (None, None, None, None, None, None, None, None, *[views[n] for n in plan["order"]])
-
-
-def unet_forward_train(model, mu: Tensor, t: Tensor, c_in=None, c_skip=None, c_out=None) -> Tensor:
-    """x_hat = c_skip*mu + c_out*f(c_in*mu, t) (or f(mu, t)) with gradients w.r.t. the model parameters.  In `train()` mode
-    the residual blocks' nn.Dropout (residual_block.py:46) is applied with a counter-based mask seeded from
-    `torch.initial_seed()` and a per-model call counter."""
-    p = float(model._dropout or 0.0) if model.training else 0.0
-    seed = 0
-    if p > 0.0:
-        model._drop_calls = getattr(model, "_drop_calls", 0) + 1
-        seed = (torch.initial_seed() * 0x9E3779B1 + model._drop_calls * 0x85EBCA77) & 0xFFFFFFFFFFFFFFFF
-    params = [q for _, q in model.named_parameters()]
-    return _UNetTrainFn.apply(model, p, seed, mu, t, c_in, c_skip, c_out, *params)
+def engine_backward(model, ctx, g_out: Tensor, flat):
+    """`bsi_unet_backward` into `flat` (a trainer's gradient buffer, or None for a fresh one): (flat, views, order) of
+    `flat_grad_views`."""
+    lib = N.lib()
+    B = ctx.B
+    cfg, w, _, _ = model.native_pack()
+    wt, _, _ = transposed_pack(model)
+    if flat is not None:
+        # persistent buffer: the views, the gradient tables and the copy jobs are built once per (buffer, parameter storage) --
+        # ~760 tensor views and ~170 descriptors per step otherwise, a few ms of host time in front of the backward's first launch
+        key = (flat.data_ptr(), flat.numel(), model._storage_key())
+        plan = model._plan_g
+        if plan is None or plan["key"] != key:
+            plan = model._plan_g = _grad_plan(model, cfg, flat, key)
+    else:
+        plan = _grad_plan(model, cfg, None, None)
+    views, g = plan["views"], plan["g"]
+    ws = torch.empty(lib.bsi_unet_backward_workspace_bytes(C.byref(cfg), B), dtype=torch.uint8, device=g_out.device)
+    N.check(lib.bsi_unet_backward(C.byref(cfg), C.byref(w), C.byref(wt), C.byref(g), B, N.ptr(g_out), N.ptr(ctx.c_out),
+                                  N.ptr(ctx.tape), N.ptr(ws), ctx.drop[0], ctx.drop[1], N.stream()))
+    ctx.tape = None
+    # the stacked FiLM gradients and the shared skip / conv2 bias gradients go to their parameters' places in the flat buffer:
+    # one launch of bsi_copy_batch_f32 instead of 167 when the buffer is the trainer's (torch._foreach_copy_ issues a hipMemcpyAsync per pair on ROCm)
+    if plan["copy_table"] is not None:
+        N.check(lib.bsi_copy_batch_f32(N.ptr(plan["copy_table"]), plan["copy_n"], plan["copy_tiles"], N.stream()))
+    else:  # a fresh gradient buffer per call (plain autograd): no table to upload, no synchronisation
+        torch._foreach_copy_(plan["copy_dst"], plan["copy_src"])
+    views["pos_map.1.weight"].copy_(plan["pm1_pad"][:, :views["pos_map.1.weight"].shape[1]])
+    return plan["flat"], views, plan["order"]

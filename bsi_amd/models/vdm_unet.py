@@ -11,6 +11,7 @@ from torch import Tensor, nn
 
 from .. import _native as N
 from ..nn import FourierFeatures
+from .native import NativeDenoiser, native_forward_train
 from .pos_emb import NyquistPositionalEmbedding
 from .utils import actfn_from_str
 
@@ -65,7 +66,7 @@ class SimplifiedUNet(nn.Module):
         self.center_block = center_block
 
 
-class DenoisingVDMUNet(nn.Module):
+class DenoisingVDMUNet(NativeDenoiser):
     """U-Net as in the VDM paper without down-sampling — same constructor as bsi.models.vdm_unet.DenoisingVDMUNet.
 
     The engines run `dim` 64, 128 and 256.  `n_attention_heads` (the centre Attention2D) runs natively for every count whose head dim
@@ -120,13 +121,6 @@ class DenoisingVDMUNet(nn.Module):
         self._dropout = dropout
         self.actfn = actfn
         self._act_code = N.ACT_CODES[actfn]  # bsi_unet_weights.actfn: every ActFn site of the engines (no parameters, no state-dict key)
-        self._pack = None
-        self._pack_key = None
-        self._pack_t = None
-        self._pack_t_key = None
-        self._plan = None
-        self._plan_t = None
-        self._ws = None
 
     # ------------------------------------------------------------------------------------------------
     def _config(self) -> N.UNetConfig:
@@ -136,39 +130,10 @@ class DenoisingVDMUNet(nn.Module):
         return N.UNetConfig(Cc, H, W, a["dim"], a["levels"], a["heads"], ff.n_min if ff is not None else 1,
                             ff.n_max if ff is not None else 0, self.pos_emb.size, a["c_dim"], a["block_heads"])
 
-    _NATIVE_CACHES = ("_pack", "_pack_key", "_pack_t", "_pack_t_key", "_plan", "_plan_t", "_plan_g", "_ws", "_last_flat_grad", "_grad_buffer")
-
-    def __deepcopy__(self, memo):
-        """`copy.deepcopy(model)` (EMA copies, checkpoint tooling) after the model has run: the native caches hold ctypes tables with raw
-        device pointers into THIS model's buffers -- they are neither picklable nor valid for a copy, and are rebuilt on first use."""
-        import copy
-        saved = {k: self.__dict__.pop(k) for k in self._NATIVE_CACHES if k in self.__dict__}
-        try:
-            cls = self.__class__
-            new = cls.__new__(cls)
-            memo[id(self)] = new
-            new.__dict__ = copy.deepcopy(self.__dict__, memo)
-            for k in saved:
-                new.__dict__[k] = None
-        finally:
-            self.__dict__.update(saved)
-        return new
-
-    def _weights_key(self):
-        ps = list(self.parameters())
-        return (ps[0].device, ps[0].data_ptr(), sum(p._version for p in ps))
-
     def _blocks(self):
         u = self.u_net
         return ([b[0] for b in u.downsampling_blocks] + [u.center_block[0], u.center_block[2]] +
                 [b[0] for b in u.upsampling_blocks])
-
-    def _storage_key(self):
-        """Identity of the parameters' STORAGE: the pack plan bakes every parameter's raw pointer into device-side descriptor
-        tables, so the key names every one of them (330 integers; a re-pack costs far more) -- replacing the storage of an
-        interior parameter (`p.data = ...`, `load_state_dict(assign=True)`, a per-module `.to()`) must rebuild the plan."""
-        ps = list(self.parameters())
-        return (ps[0].device, len(ps), hash(tuple(p.data_ptr() for p in ps)))
 
     def native_pack(self):
         """(config, weight table, block array, keep-alive) for the HIP engines.  The bf16 shadows live in PERSISTENT buffers described
@@ -178,10 +143,7 @@ class DenoisingVDMUNet(nn.Module):
         key = self._weights_key()
         if self._pack is not None and self._pack_key == key:
             return self._pack
-        skey = self._storage_key()
-        if getattr(self, "_plan", None) is None or self._plan["skey"] != skey:
-            self._plan = self._build_plan(skey)
-        plan = self._plan
+        plan = self._current_plan()
         lib = N.lib()
         with torch.no_grad():
             N.check(lib.bsi_conv_weight_pack_batch(N.ptr(plan["descs"]), plan["ndesc"], 0, N.stream()))
@@ -270,17 +232,12 @@ class DenoisingVDMUNet(nn.Module):
         w.blocks = C.cast(arr, C.POINTER(N.UNetResBlockWeights))
         w.actfn = self._act_code
         darr = (N.ConvPackDesc * len(descs))(*descs)
-        descs_dev = torch.frombuffer(bytearray(bytes(darr)), dtype=torch.uint8).to(dev)
+        descs_dev = N.upload_table(darr, dev)
         keep.extend([b2_dst, b2_tmp, film_w_cat, film_b_cat, descs_dev, film_ws, film_bs])
         return {"skey": skey, "pack": (cfg, w, arr, keep), "descs": descs_dev, "ndesc": len(descs), "casts": casts,
                 "b2_dst": b2_dst, "b2_tmp": b2_tmp, "b2_a": [blocks[i].layers[-1].bias.detach() for i in skips],
                 "b2_b": [blocks[i].skip.bias.detach() for i in skips], "film_ws": film_ws, "film_bs": film_bs,
                 "film_w_cat": film_w_cat, "film_b_cat": film_b_cat}
-
-    def _workspace(self, nbytes: int, dev):
-        if self._ws is None or self._ws.numel() < nbytes or self._ws.device != dev:
-            self._ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        return self._ws
 
     def adaln_table(self, t: Tensor) -> Tensor:
         """Conditioning table for the times `t` ([R]): FiLM (scale, shift) of every residual block,
@@ -299,27 +256,29 @@ class DenoisingVDMUNet(nn.Module):
                        out: Tensor | None = None):
         cfg, w, _, _ = self.native_pack()
         lib = N.lib()
-        if mu.dtype != torch.float32:
-            raise RuntimeError("bsi_amd.DenoisingVDMUNet: input must be fp32 (bf16 is used inside the kernels)")
-        mu = mu.contiguous()
-        B = mu.shape[0]
-        assert tuple(mu.shape[1:]) == self.data_shape, f"expected [B,{self.data_shape}], got {tuple(mu.shape)}"
-        if out is None:
-            out = torch.empty_like(mu)
+        mu, B, out = self._prepare_input(mu, out)
         ws = self._workspace(lib.bsi_unet_workspace_bytes(C.byref(cfg), B), mu.device)
         N.check(lib.bsi_unet_forward(C.byref(cfg), C.byref(w), B, N.ptr(mu), N.ptr(mod), mod.shape[0], N.ptr(c_in),
                                      N.ptr(c_skip), N.ptr(c_out), coef_stride, N.ptr(out), N.ptr(ws), N.stream()))
         return out
 
-    def forward(self, mu: Tensor, t: Tensor) -> Tensor:
-        """f(mu, t): mu [B, *data_shape] fp32, t [B] in [0, 1]  (vdm_unet.py:92-100)."""
-        if not mu.is_cuda:
-            raise RuntimeError("bsi_amd.DenoisingVDMUNet: input is not on a HIP device; there is no CPU path")
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
-            return self.forward_train(mu, t)  # backward kernels live in the training engine
-        return self.forward_native(mu, self.adaln_table(t))
-
     def forward_train(self, mu: Tensor, t: Tensor, c_in=None, c_skip=None, c_out=None) -> Tensor:
-        """Differentiable evaluation (parameters only): tape-recording HIP forward + hand-written HIP backward."""
-        from .unet_train import unet_forward_train
-        return unet_forward_train(self, mu, t, c_in, c_skip, c_out)
+        """Differentiable evaluation (parameters only): tape-recording HIP forward + hand-written HIP backward.  In `train()` mode
+        the residual blocks' nn.Dropout (residual_block.py:46) is applied with a counter-based mask."""
+        p = float(self._dropout or 0.0) if self.training else 0.0
+        return native_forward_train(self, p, mu, t, c_in, c_skip, c_out)
+
+    def _tape_bytes(self, cfg, B):
+        return N.lib().bsi_unet_tape_bytes(C.byref(cfg), B)
+
+    def _engine_train_forward(self, cfg, w, B, mu, t, c_in, c_skip, c_out, out, tape, drop_p, seed):
+        N.check(N.lib().bsi_unet_train_forward(C.byref(cfg), C.byref(w), B, N.ptr(mu), N.ptr(t), N.ptr(c_in), N.ptr(c_skip),
+                                               N.ptr(c_out), N.ptr(out), N.ptr(tape), drop_p, seed, N.stream()))
+
+    def _engine_backward(self, ctx, g_out, flat):
+        from .unet_train import engine_backward  # the gradient tables live with the training engine
+        return engine_backward(self, ctx, g_out, flat)
+
+    def _build_plan_t(self, skey):
+        from .unet_train import build_plan_t
+        return build_plan_t(self, skey)

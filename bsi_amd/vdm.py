@@ -9,6 +9,7 @@ from torch import Tensor, nn
 
 from . import _native as N
 from .bsi import Discretization, _new, _PredictCombine, _SqErr
+from .models.native import native_denoiser
 
 
 class VDM(nn.Module):
@@ -57,8 +58,7 @@ class VDM(nn.Module):
         return out
 
     def _native_model(self):
-        m = self.model
-        return m if hasattr(m, "forward_native") and hasattr(m, "adaln_table") else None
+        return native_denoiser(self.model)
 
     # -- schedule functions (vdm.py:138-150) ------------------------------------------------------------
     def gamma(self, t: Tensor) -> Tensor:

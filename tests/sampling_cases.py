@@ -35,8 +35,8 @@ def digest(t):
             "sample": [int(v) for v in w[::step][:SAMPLE]]}
 
 
-def load_fixture():
-    with open(FIXTURE) as f:
+def load_fixture(path=FIXTURE):
+    with open(path) as f:
         return json.load(f)
 
 
